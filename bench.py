@@ -7,7 +7,9 @@ evaluates all four terms, and so do we).  One step = TensorBoardTrainerEnhanced:
 (enhanced.h:287-304): forward, loss + dL/dpred, backward, clip_grad_norm_(1.0), Adam — all in
 libcad_hip.so.  Synthetic SUN-RGB-D-shaped batches resident in HBM (data loading excluded).
 
-  python bench.py [--gpus N --steps K --warmup W]      # configs[1] (the headline line)
+  python bench.py [--gpus N --steps K --warmup W]      # configs[1] (the headline line), nothing else
+  python bench.py --full [...]                          # + roofline, cpu_baseline, parity, other workloads
+  python bench.py --dump-outputs DIR [...]              # + the last timed step's outputs as DIR/<name>.npy
   python bench.py --config 3                            # ray+FiLM model, bf16 GEMMs, full loss
   python bench.py --config 4                            # baseline_unet, bf16 GEMMs, full loss
   N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N  (one rank per GPU,
@@ -15,7 +17,11 @@ libcad_hip.so.  Synthetic SUN-RGB-D-shaped batches resident in HBM (data loading
   buckets all-reduced on its own stream while the backward runs, the build/train path; torch.distributed
   only hands over the unique id and keeps the host-side barrier / max-over-ranks clock).
 
-Rank 0 prints ONE JSON line.  roofline: the dominant MFMA kernel (largest total time in the timed
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+fields (value, ms_per_step, last_loss, config; with N>1 the exchange accounting of the timed steps);
+everything below runs only with --full (and is null in a plain run's line).
+--dump-outputs DIR: after the timed steps, what the last of them handed its caller (dump_outputs).
+roofline: the dominant MFMA kernel (largest total time in the timed
 region, timed live with HIP events on its launch stream) against its engine's MFMA ceiling.
 cpu_baseline: the oracle restatement (LibTorch CPU, the reference's ATen kernels) on a bounded
 sample of the workload on this host's physical cores (plus a thread-count sweep); parity: 10
@@ -73,8 +79,16 @@ def parse():
     ap.add_argument("--model", default=None, choices=("baseline", "film", "rayfilm"))
     ap.add_argument("--dtype", default=None, choices=("fp32", "bf16"),
                     help="GEMM arithmetic: fp32 (S3 engine, fp32-accurate) or bf16 operands / fp32 accumulation")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the bf16 workload legs and the data path")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline of the dominant kernel "
+                         "(a census step + events in the timed region), the CPU baseline and parity steps, the other "
+                         "workloads and the data path (N>1: the DP workloads)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (prediction, loss terms, gradient norm, a sample of the "
+                         "updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity legs")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the bf16 workload legs and the data path")
     ap.add_argument("--exchange", default="rccl", choices=("rccl", "torch"),
                     help="N>1 gradient exchange: libcad's RCCL communicator (the build/train path) or torch.distributed")
     # 1 warm-up + >= 3 timed steps at bs32 480x640, on the job's CPU share
@@ -620,6 +634,45 @@ def data_path(cad, dev, B, H, W, h0=530, w0=730, reps=10):
             "achieved_GBps": round(per_img * B / ms / 1e6, 1), "peak_GBps": HBM_PEAK_GBS}
 
 
+DUMP_PRED_ELEMS = 12 << 20    # 48 MiB of float32: the headline's (32, 1, 480, 640) prediction fits whole
+DUMP_PARAM_ELEMS = 1 << 20    # 4 MiB: a sample of the 31 M updated parameters
+DUMP_SEED = 0x5EED
+
+
+def dump_sample(a, limit):
+    """`a` whole when it has at most `limit` elements, else a fixed sample of it: `limit` sorted flat
+    indices drawn (with replacement) from default_rng(DUMP_SEED), the same for every run of one shape."""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.size <= limit:
+        return a
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, size=limit))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(dirpath, trainer, model):
+    """--dump-outputs: what the last timed train step handed its caller, one float32 DIR/<name>.npy each
+    (under 64 MB in all), so that two builds run with the same arguments (the synthetic batch and
+    the initial weights are fixed streams) can be compared output for output:
+      pred         the step's train-mode prediction (B, 1, H, W) (Trainer.pred)
+      loss5        total, si, grad, smooth, reproj of that prediction (train_step's return value)
+      grad_norm    the gradient norm clip_grad_norm_ measured in that step
+      params       the parameters after that step's Adam update, named_parameters() order, flattened
+                   (a seeded sample of DUMP_PARAM_ELEMS of them)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize(model.device)
+    os.makedirs(dirpath, exist_ok=True)
+    params = np.concatenate([v.numpy().reshape(-1) for v in model.named_parameters().values()])
+    arrays = {"pred": dump_sample(trainer.pred.cpu().numpy(), DUMP_PRED_ELEMS),
+              "loss5": dump_sample(trainer.loss5.cpu().numpy(), 5),
+              "grad_norm": np.array([model.last_grad_norm()], dtype=np.float32),
+              "params": dump_sample(params, DUMP_PARAM_ELEMS)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def setup_dist(args):
     """N>1: one rank per GPU.  torch.distributed (gloo, host memory only) is the launcher's store and
     the host-side barrier / max-over-ranks clock; the gradient exchange itself is libcad's RCCL
@@ -811,18 +864,24 @@ def main():
         trainer.set_exchange_timing(True)
     for i in range(args.warmup):
         trainer.train_step(rgb, gt, K)
-    # one more untimed step with every GEMM launch timed names the dominant kernel; the timed region
-    # then brackets only that kernel's launches with events (every rank runs it: collectives)
-    census = gemm_census(lib, lambda: trainer.train_step(rgb, gt, K), dev)
+    # --full: one more untimed step with every GEMM launch timed names the dominant kernel; the timed
+    # region then brackets only that kernel's launches with events (every rank runs it: collectives)
+    census = gemm_census(lib, lambda: trainer.train_step(rgb, gt, K), dev) if args.full else None
     xstats = trainer.exchange_stats if world > 1 else None
     if xstats:
         xstats()   # warm-up and census steps are not accounted
-    with profiled(lib, dominant_name(census)) as prof:
+    if args.full:
+        with profiled(lib, dominant_name(census)) as prof:
+            elapsed = timed_region(lambda: trainer.train_step(rgb, gt, K), args.steps, 0, world, dev)
+    else:
         elapsed = timed_region(lambda: trainer.train_step(rgb, gt, K), args.steps, 0, world, dev)
     exchange = exchange_report(xstats(), args.steps, world) if xstats else None
     last_loss = trainer.loss5[0].item()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, trainer, model)
     dp_legs = None
-    if world > 1 and not args.no_extra:
+    if world > 1 and args.full and not args.no_extra:
         # the DP workloads BASELINE names for the multi-GPU runs (configs[3], configs[4]) with the same
         # exchange; every rank runs them, rank 0 reports
         del trainer, loss, model
@@ -843,14 +902,14 @@ def main():
         images = B * world * args.steps
         value = images / elapsed
         ms_per_step = 1e3 * elapsed / args.steps
-        roof = roofline_of(prof(), args.steps, ms_per_step, show=True, census=census)
+        roof = roofline_of(prof(), args.steps, ms_per_step, show=True, census=census) if args.full else None
         step_tflops = (FLOP_PER_IMAGE_480x640_F64 * value / 1e12
                        if (H, W, f, args.model) == (480, 640, 64, "baseline") else None)
         dp, extra, cpu, parity = None, None, None, None
         if dp_legs is None:
             del trainer, loss, model
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             extra = {}
             for cfg in (3, 4):
                 if cfg == args.config:
@@ -882,7 +941,7 @@ def main():
                 dp = data_path(cad, dev, B, H, W)
             except Exception as e:
                 log(f"data-path measurement failed: {e}")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(args)
                 log(f"cpu baseline: {cpu}")
@@ -897,6 +956,7 @@ def main():
             "metric": METRIC, "value": round(value, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic (SUN-RGB-D-shaped, HBM-resident)",
+            "full": args.full, "dumped_outputs": dumped,
             "config": {"workload": WORKLOADS[args.config] if (args.model, args.dtype) == PRESETS[args.config] else
                        f"{args.model} train step, {args.dtype} GEMMs, bs{B}/GPU {H}x{W}, loss weights {args.weights}",
                        "model": args.model,

@@ -20,7 +20,7 @@ if [ "$CFG" = 5 ] || [ "$CFG" = 5x8 ]; then
     PROG="profiles/c5_step.py $X8"
     ARGS="--steps 3 --warmup 1"; ARGS1="--steps 1 --warmup 1"
 else
-    PROG="bench.py --no-cpu-baseline --no-extra --config $CFG"
+    PROG="bench.py --full --no-cpu-baseline --no-extra --config $CFG"
     ARGS="--steps 3 --warmup 1"; ARGS1="--steps 1 --warmup 0"
 fi
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \

@@ -69,7 +69,7 @@ def test_bench_two_ranks_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--exchange", "torch", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64",
-           "--width", "64", "--features", "8", "--no-cpu-baseline"]
+           "--width", "64", "--features", "8", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -37,7 +37,7 @@ for rep in range(args.reps):
                    *args.extra.split()]
         else:
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(args.config), "--steps",
-                   str(args.steps), "--warmup", "3", "--no-cpu-baseline", "--no-extra", *args.extra.split()]
+                   str(args.steps), "--warmup", "3", "--full", "--no-cpu-baseline", "--no-extra", *args.extra.split()]
         r = subprocess.run(cmd, capture_output=True, text=True, env=env_of(spec), timeout=600)
         if r.returncode != 0:
             print(json.dumps({"arm": arm, "spec": spec, "error": r.stderr[-2000:]}), flush=True)
