@@ -52,6 +52,20 @@ class ArchiveEntry(C.Structure):
                 ("data", C.c_void_p)]
 
 
+class EvalConfig(C.Structure):
+    """cad_eval_config (cad.h): DepthMetrics::compute's depth range and prediction clamp."""
+    _fields_ = [("min_depth", F), ("max_depth", F), ("clamp_pred", I)]
+
+
+EVAL_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "mae", "log10", "delta_1.25", "delta_1.25^2", "delta_1.25^3",
+             "num_valid_pixels", "mean_pred_depth", "mean_gt_depth")
+
+
+class EvalSummary(C.Structure):
+    """cad_eval_summary (cad.h)."""
+    _fields_ = [("count", I64)] + [(k, F * 12) for k in ("mean", "std", "median", "min", "max", "pooled")]
+
+
 # name: (restype, argtypes)
 SIGNATURES = {
     "cad_abi_version": (I, []),
@@ -148,6 +162,18 @@ SIGNATURES = {
     "cad_loss_forward_backward": (I, [P, P, P, P, P, I, P, P, P]),
     "cad_loss_get_components": (I, [P, FP, P]),
     "cad_depth_metrics": (I, [P, P, I, I, I, FP, P]),
+    "cad_event_create": (I, [C.POINTER(P)]),
+    "cad_event_destroy": (None, [P]),
+    "cad_event_record": (I, [P, P]),
+    "cad_event_elapsed_ms": (I, [P, P, FP]),
+    "cad_evaluator_create": (I, [I64, I, I, I, C.POINTER(EvalConfig), I, C.POINTER(P)]),
+    "cad_evaluator_destroy": (None, [P]),
+    "cad_evaluator_reset": (I, [P]),
+    "cad_evaluator_update": (I, [P, P, P, P, I, P]),
+    "cad_evaluator_count": (I64, [P]),
+    "cad_evaluator_sums": (I, [P, C.POINTER(C.c_double), P]),
+    "cad_evaluator_metrics": (I, [P, FP, C.POINTER(EvalSummary)]),
+    "cad_eval_finish": (I, [C.POINTER(C.c_double), I64, FP, C.POINTER(EvalSummary)]),
     "cad_ray_directions": (I, [P, I, I, I, P, P]),
     "cad_unet_debug_buffer": (I64, [P, C.c_char_p, FP, I64]),
     "cad_profile_enable": (I, [I]),

@@ -1,0 +1,357 @@
+// build/evaluate — offline evaluation of a trained checkpoint, after the reference's evaluate target
+// (src/evaluation/evaluate_main.cpp:283-297 flags, :214-278 report), which does not build there; on
+// libcad_hip.so through include/cad/evaluator.hpp (ModelEvaluator over the device-resident metrics table).
+//
+//   build/evaluate -c <final_model.pt | .cadckpt> -g <train_config.yaml> [-o results/eval] [--data-dir D]
+//                  [--split val|train] [--save-predictions] [--gpu 0] [--dry-run]
+//   build/evaluate --compare A/per_sample.csv B/per_sample.csv [--metric abs_rel] [--seed 42]
+//
+// The model (model.architecture, init_features, max_depth, variant, use_pcl, use_attention), the data
+// section and training.batch_size come from the training YAML, the keys build/train reads; the synthetic
+// dataset works as it does for training (val: num_val_samples generated with seed + 1, the trainer's
+// validation split; train: num_train_samples with the seed).  On the manifest, val takes the first
+// min(500, size) samples like validateEpoch and train all of them, both without augmentation.
+// Writes summary.csv, per_sample.csv, report.txt (the reference's report without its timing block, whose
+// per-image numbers need host timing around each forward) and, with --save-predictions, pred_<index>.npy
+// (fp32, H x W).  Any exception prints "Error: <what>" and exits 1, like build/train.
+#include <cstdio>
+#include <cstdlib>
+#include <ctime>
+#include <filesystem>
+#include <fstream>
+#include <iomanip>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../../include/cad/cad.hpp"
+#include "../../../include/cad/eval_stats.hpp"
+#include "../../../include/cad/evaluator.hpp"
+#include "../host/yaml_lite.hpp"
+
+namespace fs = std::filesystem;
+using namespace camera_aware_depth;
+
+namespace {
+
+struct Args {
+    std::string checkpoint, config, output = "results/eval", data_dir, split = "val", metric = "abs_rel";
+    std::vector<std::string> compare;
+    int gpu = 0;
+    uint32_t seed = 42;
+    bool save_predictions = false, dry_run = false;
+};
+
+void usage() {
+    std::cout << "evaluate - Evaluate a trained depth estimation model (MI355X)\n"
+                 "  -c, --checkpoint arg  Path to model checkpoint (.pt torch::save archive or .cadckpt)\n"
+                 "  -g, --config arg      Path to the training config YAML\n"
+                 "  -o, --output arg      Output directory for results (default: results/eval)\n"
+                 "      --data-dir arg    Data directory (overrides the config)\n"
+                 "      --split arg       val or train (default: val)\n"
+                 "      --save-predictions  Save every depth prediction as pred_<index>.npy\n"
+                 "      --gpu arg         GPU ID (default: 0)\n"
+                 "      --dry-run         Print the evaluation plan and exit; no GPU use\n"
+                 "      --compare A B     Paired comparison of two per_sample.csv files (no GPU use)\n"
+                 "      --metric arg      Column compared by --compare (default: abs_rel)\n"
+                 "      --seed arg        Bootstrap seed of --compare (default: 42)\n"
+                 "  -h, --help            Print help\n";
+}
+
+Args parse_args(int argc, char** argv) {
+    Args a;
+    for (int i = 1; i < argc; ++i) {
+        std::string k = argv[i], v;
+        auto eq = k.find('=');
+        if (k.rfind("--", 0) == 0 && eq != std::string::npos) { v = k.substr(eq + 1); k = k.substr(0, eq); }
+        auto next = [&]() -> std::string {
+            if (!v.empty()) return v;
+            if (i + 1 >= argc) throw std::runtime_error("missing value for " + k);
+            return argv[++i];
+        };
+        if (k == "-h" || k == "--help") { usage(); std::exit(0); }
+        else if (k == "-c" || k == "--checkpoint") a.checkpoint = next();
+        else if (k == "-g" || k == "--config") a.config = next();
+        else if (k == "-o" || k == "--output") a.output = next();
+        else if (k == "--data-dir") a.data_dir = next();
+        else if (k == "--split") a.split = next();
+        else if (k == "--save-predictions") a.save_predictions = true;
+        else if (k == "--gpu") a.gpu = std::stoi(next());
+        else if (k == "--dry-run") a.dry_run = true;
+        else if (k == "--metric") a.metric = next();
+        else if (k == "--seed") a.seed = (uint32_t)std::stoul(next());
+        else if (k == "--compare") {
+            a.compare.push_back(next());
+            if (i + 1 >= argc) throw std::runtime_error("--compare takes two per_sample.csv files");
+            a.compare.push_back(argv[++i]);
+        } else throw std::runtime_error("unknown option " + k);
+    }
+    return a;
+}
+
+struct Config {   // the keys of train_main.cpp's load_config that evaluation needs
+    int batch_size = 8, init_features = 64, height = 240, width = 320, seed = 42, n_train = 64, n_val = 16;
+    float max_depth = 10.0f;
+    std::string architecture = "baseline_unet", variant = "full", dataset = "sunrgbd", data_dir = "./data/sunrgbd",
+                manifest_path = "./data/sunrgbd_manifest.json";
+    bool use_pcl = true, use_attention = true;
+    std::vector<std::string> sensor_types;
+};
+
+Config load_config(const yaml_lite::Node& y) {
+    Config c;
+    if (auto& t = y["training"]) c.batch_size = t["batch_size"].as<int>(8);
+    if (auto& e = y["experiment"]) c.seed = e["seed"].as<int>(42);
+    if (auto& m = y["model"]) {
+        c.init_features = m["init_features"].as<int>(64);
+        c.max_depth = m["max_depth"].as<float>(10.0f);
+        c.architecture = m["architecture"].as<std::string>("baseline_unet");
+        c.variant = m["variant"].as<std::string>("full");
+        c.use_pcl = m["use_pcl"].as<bool>(true);
+        c.use_attention = m["use_attention"].as<bool>(true);
+        if (c.architecture != "baseline_unet" && c.architecture != "intrinsics_unet" && c.architecture != "ray_film_unet" &&
+            c.architecture != "geometry_aware")
+            throw std::runtime_error("model.architecture '" + c.architecture +
+                                     "': this CLI evaluates baseline_unet, intrinsics_unet, ray_film_unet or geometry_aware");
+        if (c.architecture == "geometry_aware" && c.variant != "full" && c.variant != "lightweight")
+            throw std::runtime_error("model.variant '" + c.variant + "': expected full or lightweight");
+    }
+    if (auto& d = y["data"]) {
+        c.height = d["input_height"].as<int>(240);
+        c.width = d["input_width"].as<int>(320);
+        c.dataset = d["dataset_name"].as<std::string>("sunrgbd");
+        c.n_train = d["num_train_samples"].as<int>(64);
+        c.n_val = d["num_val_samples"].as<int>(16);
+        c.manifest_path = d["manifest_path"].as<std::string>("./data/sunrgbd_manifest.json");
+        c.data_dir = d["data_dir"].as<std::string>("./data/sunrgbd");
+        c.sensor_types = d["sensor_types"].as<std::vector<std::string>>({});
+    }
+    if (c.batch_size < 1) throw std::runtime_error("training.batch_size must be positive");
+    return c;
+}
+
+bool ends_with(const std::string& s, const std::string& suf) {
+    return s.size() >= suf.size() && s.compare(s.size() - suf.size(), suf.size(), suf) == 0;
+}
+
+// ---- --compare: two per_sample.csv files, paired by their index column ----
+struct Column {
+    std::vector<long long> index;
+    std::vector<double> value;
+};
+Column read_column(const std::string& path, const std::string& metric) {
+    std::ifstream f(path);
+    if (!f) throw std::runtime_error("Cannot open " + path);
+    std::string line, cell;
+    if (!std::getline(f, line)) throw std::runtime_error(path + " is empty");
+    int col = -1, n = 0;
+    for (std::stringstream hs(line); std::getline(hs, cell, ','); ++n) {
+        if (n == 0 && cell != "index") throw std::runtime_error(path + ": the first column must be index");
+        if (cell == metric) col = n;
+    }
+    if (col < 1) throw std::runtime_error(path + " has no column '" + metric + "'");
+    Column c;
+    while (std::getline(f, line)) {
+        if (line.empty()) continue;
+        std::stringstream ls(line);
+        for (int i = 0; std::getline(ls, cell, ','); ++i) {
+            if (i == 0) c.index.push_back(std::stoll(cell));
+            if (i == col) c.value.push_back(std::stod(cell));
+        }
+        if (c.index.size() != c.value.size()) throw std::runtime_error(path + ": short row '" + line + "'");
+    }
+    return c;
+}
+
+int compare(const Args& a) {
+    const Column x = read_column(a.compare[0], a.metric), y = read_column(a.compare[1], a.metric);
+    if (x.index.size() != y.index.size())
+        throw std::runtime_error("the files hold " + std::to_string(x.index.size()) + " and " +
+                                 std::to_string(y.index.size()) + " samples: a paired comparison needs the same samples");
+    if (x.index != y.index) throw std::runtime_error("the sample indices of the two files do not match");
+    if (x.value.size() < 2) throw std::runtime_error("a paired comparison needs at least two samples");
+    std::cout << eval_stats::compare_models(x.value, y.value, a.compare[0], a.compare[1], a.metric, a.seed);
+    return 0;
+}
+
+// ---- outputs ----
+void write_npy(const std::string& path, const float* data, int H, int W) {
+    std::string head = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + std::to_string(H) + ", " + std::to_string(W) +
+                       "), }";
+    while ((10 + head.size() + 1) % 64 != 0) head += ' ';
+    head += '\n';
+    std::ofstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    const unsigned char pre[8] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0};
+    const uint16_t hl = (uint16_t)head.size();
+    f.write((const char*)pre, 8);
+    f.write((const char*)&hl, 2);
+    f.write(head.data(), (std::streamsize)head.size());
+    f.write((const char*)data, (std::streamsize)sizeof(float) * H * W);
+}
+
+void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
+    const auto& keys = metricKeys();
+    {
+        std::ofstream f(a.output + "/per_sample.csv");
+        if (!f) throw std::runtime_error("cannot write " + a.output + "/per_sample.csv");
+        f << "index";
+        for (const char* k : keys) f << "," << k;
+        f << "\n" << std::setprecision(9);
+        for (size_t i = 0; i < r.sample_results.size(); ++i) {
+            f << i;
+            for (int k = 0; k < CAD_EVAL_METRICS; ++k) f << "," << r.per_sample[i * CAD_EVAL_METRICS + (size_t)k];
+            f << "\n";
+        }
+    }
+    {
+        std::ofstream f(a.output + "/summary.csv");
+        if (!f) throw std::runtime_error("cannot write " + a.output + "/summary.csv");
+        f << "num_samples";
+        for (const char* k : keys)
+            for (const char* s : {"mean", "std", "median", "pooled"}) f << "," << k << "_" << s;
+        f << "\n" << std::setprecision(9) << r.sample_results.size();
+        for (const char* k : keys)
+            for (const MetricMap* m : {&r.mean_metrics, &r.std_metrics, &r.median_metrics, &r.pooled_metrics}) f << "," << m->at(k);
+        f << "\n";
+    }
+    std::ofstream rep(a.output + "/report.txt");
+    if (!rep) throw std::runtime_error("cannot write " + a.output + "/report.txt");
+    const std::time_t now = std::time(nullptr);
+    const std::string bar(65, '='), rule(65, '-');
+    rep << bar << "\n                  Model Evaluation Report\n" << bar << "\n\n";
+    rep << "Checkpoint: " << a.checkpoint << "\n";
+    rep << "Model Type: " << c.architecture << (c.architecture == "geometry_aware" ? "/" + c.variant : std::string()) << "\n";
+    rep << "Parameters: " << r.num_parameters << "\n";
+    rep << "Test Samples: " << r.sample_results.size() << " (" << a.split << ")\n";
+    rep << "Evaluation Date: " << std::put_time(std::localtime(&now), "%Y-%m-%d %H:%M:%S") << "\n\n";
+    rep << rule << "\n                    Performance Metrics\n" << rule << "\n\n";
+    rep << std::fixed << std::setprecision(4);
+    const auto pm = [&](const char* label, const char* k) {
+        rep << label << r.mean_metrics.at(k) << " ± " << r.std_metrics.at(k) << "\n";
+    };
+    rep << "Lower is better:\n";
+    pm("  AbsRel:   ", "abs_rel");
+    pm("  SqRel:    ", "sq_rel");
+    pm("  RMSE:     ", "rmse");
+    pm("  RMSElog:  ", "rmse_log");
+    pm("  MAE:      ", "mae");
+    pm("  Log10:    ", "log10");
+    rep << "\nHigher is better (Accuracy thresholds):\n";
+    pm("  δ < 1.25:    ", "delta_1.25");
+    pm("  δ < 1.25²:   ", "delta_1.25^2");
+    pm("  δ < 1.25³:   ", "delta_1.25^3");
+    rep << "\n" << rule << "\n                   Inference Performance\n" << rule << "\n\n";
+    rep << "  Mean Time:   " << r.forward_ms_per_image << " ms per image (device time of the whole loop, batch "
+        << c.batch_size << ")\n";
+    rep << "  FPS:         " << (r.forward_ms_per_image > 0 ? 1000.0 / r.forward_ms_per_image : 0.0) << "\n\n";
+    rep << rule << "\n                     Median Metrics\n" << rule << "\n\n";
+    rep << "  AbsRel:   " << r.median_metrics.at("abs_rel") << "\n";
+    rep << "  RMSE:     " << r.median_metrics.at("rmse") << "\n";
+    rep << "  RMSElog:  " << r.median_metrics.at("rmse_log") << "\n";
+    rep << "  δ < 1.25: " << r.median_metrics.at("delta_1.25") << "\n\n";
+    rep << rule << "\n              Pooled Over All Valid Pixels\n" << rule << "\n\n";
+    rep << formatMetrics(r.pooled_metrics) << "\n" << bar << "\n";
+}
+
+int run(const Args& a) {
+    if (!a.compare.empty()) return compare(a);
+    if (a.checkpoint.empty() || a.config.empty()) throw std::runtime_error("--checkpoint and --config are required");
+    if (a.split != "val" && a.split != "train") throw std::runtime_error("--split '" + a.split + "': expected val or train");
+    if (!fs::exists(a.checkpoint)) throw std::runtime_error("Cannot open checkpoint: " + a.checkpoint);
+    const bool pt = ends_with(a.checkpoint, ".pt");
+    if (!pt && !ends_with(a.checkpoint, ".cadckpt"))
+        throw std::runtime_error("checkpoint '" + a.checkpoint + "': expected a .pt or .cadckpt file");
+    Config c = load_config(yaml_lite::load_file(a.config));
+    if (!a.data_dir.empty()) c.data_dir = a.data_dir;
+    const bool geo = c.architecture == "geometry_aware";
+    if (geo && pt) throw std::runtime_error("geometry_aware checkpoints are .cadckpt files");
+    const bool real = c.dataset != "synthetic";
+    int64_t ns = a.split == "val" ? c.n_val : c.n_train;
+    if (real) {   // the sample count, read on the host before any GPU call
+        std::vector<const char*> sens;
+        for (const auto& x : c.sensor_types) sens.push_back(x.c_str());
+        cad_dataset* d = nullptr;
+        cad::check(cad_dataset_open(c.manifest_path.c_str(), sens.empty() ? nullptr : sens.data(), (int)sens.size(), &d),
+                   "SunRGBDLoader");
+        ns = cad_dataset_size(d);
+        cad_dataset_destroy(d);
+        if (a.split == "val") ns = std::min<int64_t>(500, ns);
+    }
+    if (ns <= 0) throw std::runtime_error("no samples to evaluate in the " + a.split + " split");
+    if (a.dry_run) {
+        std::cout << "{\"checkpoint\": \"" << a.checkpoint << "\", \"format\": \"" << (pt ? "torch" : "cadckpt")
+                  << "\", \"architecture\": \"" << c.architecture << "\", \"init_features\": " << c.init_features
+                  << ", \"max_depth\": " << c.max_depth << ", \"dataset\": \"" << (real ? c.manifest_path : "synthetic")
+                  << "\", \"split\": \"" << a.split << "\", \"samples\": " << ns << ", \"batch_size\": " << c.batch_size
+                  << ", \"batches\": " << (ns + c.batch_size - 1) / c.batch_size << ", \"height\": " << c.height
+                  << ", \"width\": " << c.width << ", \"device\": " << a.gpu << ", \"output\": \"" << a.output
+                  << "\", \"save_predictions\": " << (a.save_predictions ? "true" : "false") << "}" << std::endl;
+        return 0;
+    }
+    int ndev = 0;
+    cad::check(cad_device_count(&ndev), "device query");
+    if (a.gpu < 0 || a.gpu >= ndev) throw std::runtime_error("GPU " + std::to_string(a.gpu) + " not available");
+    cad::check(cad_set_device(a.gpu), "set device");
+    fs::create_directories(a.output);
+
+    std::shared_ptr<SunRGBDLoader> loader;
+    if (real) {
+        loader = std::make_shared<SunRGBDLoader>(c.data_dir, c.manifest_path, a.split == "val" ? "test" : "train");
+        if (!c.sensor_types.empty()) loader->filterBySensorType(c.sensor_types);
+    } else {
+        loader = SunRGBDLoader::synthetic(ns, c.height, c.width, (uint32_t)c.seed + (a.split == "val" ? 1u : 0u));
+    }
+    loader->setTargetDimensions(c.height, c.width);
+
+    EvaluationConfig ec;
+    ec.max_depth = c.max_depth;
+    ec.batch_size = c.batch_size;
+    ec.device = a.gpu;
+    ec.max_samples = ns;
+    if (a.save_predictions)
+        ec.on_batch = [&](int64_t first, const DeviceTensor& pred, int n) {
+            const std::vector<float> h = pred.to_host();
+            const int64_t hw = (int64_t)c.height * c.width;
+            for (int i = 0; i < n; ++i)
+                write_npy(a.output + "/pred_" + std::to_string(first + i) + ".npy", h.data() + i * hw, c.height, c.width);
+        };
+    const cad::Workspace ws{c.batch_size, c.height, c.width, a.gpu};
+    std::unique_ptr<ModelEvaluator> ev;
+    if (geo) {
+        std::shared_ptr<GeometryAwareNetworkImpl> m;
+        if (c.variant == "lightweight") m = std::make_shared<LightweightGeometryNetworkImpl>(3, c.init_features, 4, c.max_depth, ws);
+        else m = std::make_shared<GeometryAwareNetworkImpl>(3, c.init_features, 4, c.max_depth, c.use_pcl, c.use_attention, ws);
+        load_model_state(a.checkpoint, *m);
+        ev = std::make_unique<ModelEvaluator>(m, ec);
+    } else {
+        std::shared_ptr<BaselineUNetImpl> m;
+        if (c.architecture == "intrinsics_unet") m = std::make_shared<IntrinsicsConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
+        else if (c.architecture == "ray_film_unet") m = std::make_shared<RayConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
+        else m = std::make_shared<BaselineUNetImpl>(3, c.init_features, c.max_depth, ws);
+        if (pt) load(*m, a.checkpoint);
+        else load_model_state(a.checkpoint, *m);
+        ev = std::make_unique<ModelEvaluator>(m, ec);
+    }
+    std::cout << "Evaluating " << a.checkpoint << " (" << c.architecture << ", f=" << c.init_features << ") on " << ns << " "
+              << a.split << " samples" << (real ? " of " + c.manifest_path : std::string(" (synthetic)")) << ", batch "
+              << c.batch_size << ", MI355X device " << a.gpu << "\n";
+    const EvaluationResult r = ev->evaluate(*loader);
+    write_outputs(a, c, r);
+    std::cout << "\nMean over " << r.sample_results.size() << " samples:\n" << formatMetrics(r.mean_metrics) << "\nForward: "
+              << std::fixed << std::setprecision(3) << r.forward_ms_per_image << " ms per image, " << r.num_parameters
+              << " parameters\nResults saved to: " << a.output << "\n";
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    try {
+        return run(parse_args(argc, argv));
+    } catch (const std::exception& e) {
+        std::cerr << "Error: " << e.what() << std::endl;
+        return 1;
+    }
+}

@@ -20,6 +20,7 @@
 // RAY_FILM's enc1 reads NHWC8 [rgb | rays | 0 0] built on device from the intrinsics.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1703,6 +1704,169 @@ cad_status cad_depth_metrics(const float* pred, const float* gt, int B, int H, i
         }
         for (int q = 0; q < 7; ++q) out7[q] = (float)(acc[q] / B);
     });
+}
+
+// ---------------- timing events (hipEvent_t behind the C ABI) ----------------
+struct cad_event {
+    hipEvent_t ev = nullptr;
+};
+cad_status cad_event_create(cad_event** out) {
+    return guard([&] {
+        require(out != nullptr, "null output handle");
+        auto e = std::make_unique<cad_event>();
+        HIPCHK(hipEventCreate(&e->ev));
+        *out = e.release();
+    });
+}
+void cad_event_destroy(cad_event* ev) {
+    if (!ev) return;
+    (void)hipEventDestroy(ev->ev);
+    delete ev;
+}
+cad_status cad_event_record(cad_event* ev, void* stream) {
+    return guard([&] {
+        require(ev != nullptr, "null event");
+        HIPCHK(hipEventRecord(ev->ev, S(stream)));
+    });
+}
+cad_status cad_event_elapsed_ms(cad_event* start, cad_event* stop, float* ms) {
+    return guard([&] {
+        require(start && stop && ms, "null argument");
+        HIPCHK(hipEventSynchronize(stop->ev));
+        HIPCHK(hipEventElapsedTime(ms, start->ev, stop->ev));
+    });
+}
+
+// ---------------- offline evaluation (DepthMetrics::compute per sample, depth_metrics.h:40-141) -------
+struct cad_evaluator {
+    int device = 0, Bmax = 0, nb = 1;
+    int64_t capacity = 0, HW = 0, count = 0;
+    cad_eval_config cfg{0.1f, 10.0f, 1};
+    double* table = nullptr;   // [capacity][12]
+    double* part = nullptr;    // [Bmax][nb][12]
+    hipStream_t last = nullptr;
+};
+
+cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, const cad_eval_config* cfg, int device,
+                                cad_evaluator** out) {
+    return guard([&] {
+        require(out != nullptr, "null output handle");
+        require(capacity > 0, "evaluator capacity must be positive");
+        require(max_batch > 0, "evaluator max_batch must be positive");
+        require(H > 0 && W > 0, "evaluator H and W must be positive");
+        const cad_eval_config c = cfg ? *cfg : cad_eval_config{0.1f, 10.0f, 1};
+        require(c.min_depth > 0.f && c.min_depth < c.max_depth, "evaluator needs 0 < min_depth < max_depth");
+        HIPCHK(hipSetDevice(device));
+        auto e = std::make_unique<cad_evaluator>();
+        e->device = device; e->Bmax = max_batch; e->capacity = capacity; e->HW = (int64_t)H * W; e->cfg = c;
+        e->nb = cad::eval_blocks(e->HW);
+        const size_t tb = sizeof(double) * CAD_EVAL_METRICS * (size_t)capacity;
+        const size_t pb = sizeof(double) * CAD_EVAL_METRICS * (size_t)max_batch * e->nb;
+        HIPCHK(hipMalloc((void**)&e->table, tb + pb));
+        HIPCHK(hipMemset(e->table, 0, tb + pb));
+        e->part = e->table + (size_t)CAD_EVAL_METRICS * capacity;
+        *out = e.release();
+    });
+}
+void cad_evaluator_destroy(cad_evaluator* e) {
+    if (!e) return;
+    (void)hipFree(e->table);
+    delete e;
+}
+cad_status cad_evaluator_reset(cad_evaluator* e) {
+    return guard([&] {
+        require(e != nullptr, "null evaluator");
+        e->count = 0;
+    });
+}
+cad_status cad_evaluator_update(cad_evaluator* e, const float* pred, const float* gt, const uint8_t* mask, int B,
+                                void* stream) {
+    return guard([&] {
+        require(e && pred && gt, "null argument");
+        require(B >= 1 && B <= e->Bmax, "batch exceeds the evaluator's max_batch");
+        require(e->count + B <= e->capacity, "evaluator capacity exceeded");
+        HIPCHK(hipSetDevice(e->device));
+        cad::eval_update(pred, gt, mask, B, e->HW, e->cfg.min_depth, e->cfg.max_depth, e->cfg.clamp_pred, e->part, e->nb,
+                         e->table, e->count, S(stream));
+        HIPCHK(hipGetLastError());
+        e->count += B;
+        e->last = S(stream);
+    });
+}
+int64_t cad_evaluator_count(const cad_evaluator* e) { return e ? e->count : 0; }
+cad_status cad_evaluator_sums(cad_evaluator* e, double* out, void* stream) {
+    return guard([&] {
+        require(e && out, "null argument");
+        if (e->count == 0) return;
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipMemcpyAsync(out, e->table, sizeof(double) * CAD_EVAL_METRICS * (size_t)e->count, hipMemcpyDeviceToHost,
+                              S(stream)));
+        HIPCHK(hipStreamSynchronize(S(stream)));
+    });
+}
+
+namespace {
+// one row of sums -> the twelve metrics (depth_metrics.h:69-85; n = 0: getZeroMetrics :238-253)
+void eval_finish_row(const double* t, double* m) {
+    for (int k = 0; k < CAD_EVAL_METRICS; ++k) m[k] = 0.0;
+    const double n = t[0];
+    if (!(n > 0)) return;
+    m[0] = t[1] / n;
+    m[1] = t[2] / n;
+    m[2] = std::sqrt(t[3] / n);
+    m[3] = std::sqrt(t[4] / n);
+    m[4] = t[5] / n;
+    m[5] = t[6] / n;
+    m[6] = t[7] / n;
+    m[7] = t[8] / n;
+    m[8] = t[9] / n;
+    m[9] = n;
+    m[10] = t[10] / n;
+    m[11] = t[11] / n;
+}
+}  // namespace
+
+cad_status cad_eval_finish(const double* sums, int64_t n, float* per_sample, cad_eval_summary* s) {
+    return guard([&] {
+        require(n >= 0 && (sums || n == 0), "bad arguments");
+        std::vector<double> m((size_t)n * CAD_EVAL_METRICS);
+        for (int64_t i = 0; i < n; ++i) eval_finish_row(sums + i * CAD_EVAL_METRICS, m.data() + i * CAD_EVAL_METRICS);
+        if (per_sample)
+            for (size_t i = 0; i < m.size(); ++i) per_sample[i] = (float)m[i];
+        if (!s) return;
+        std::memset(s, 0, sizeof(*s));
+        s->count = n;
+        if (n == 0) return;
+        double pooled_sums[CAD_EVAL_METRICS] = {0}, pooled[CAD_EVAL_METRICS];
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < CAD_EVAL_METRICS; ++k) pooled_sums[k] += sums[i * CAD_EVAL_METRICS + k];
+        eval_finish_row(pooled_sums, pooled);
+        std::vector<double> col((size_t)n);
+        for (int k = 0; k < CAD_EVAL_METRICS; ++k) {
+            double sum = 0.0;
+            for (int64_t i = 0; i < n; ++i) sum += (col[(size_t)i] = m[(size_t)i * CAD_EVAL_METRICS + k]);
+            const double mean = sum / n;
+            double var = 0.0;
+            for (double v : col) var += (v - mean) * (v - mean);
+            std::sort(col.begin(), col.end());
+            s->mean[k] = (float)mean;
+            s->std[k] = (float)std::sqrt(var / n);
+            s->median[k] = (float)(n % 2 ? col[(size_t)(n / 2)] : 0.5 * (col[(size_t)(n / 2 - 1)] + col[(size_t)(n / 2)]));
+            s->min[k] = (float)col.front();
+            s->max[k] = (float)col.back();
+            s->pooled[k] = (float)pooled[k];
+        }
+    });
+}
+
+cad_status cad_evaluator_metrics(cad_evaluator* e, float* per_sample, cad_eval_summary* s) {
+    if (!e) { g_err = "null evaluator"; return CAD_ERR_INVALID; }
+    std::vector<double> sums((size_t)e->count * CAD_EVAL_METRICS);
+    if (e->count > 0) {
+        const cad_status st = cad_evaluator_sums(e, sums.data(), e->last);
+        if (st != CAD_OK) return st;
+    }
+    return cad_eval_finish(sums.data(), e->count, per_sample, s);
 }
 
 cad_status cad_camera_from_K(const float* K, int B, float* cam4, void* stream) {

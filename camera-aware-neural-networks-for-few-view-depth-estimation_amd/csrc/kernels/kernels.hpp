@@ -304,6 +304,12 @@ void head_bwd_y(const float* y, int C, const float* scale, const float* shift, c
 int metrics_blocks(int64_t HW);
 void depth_metrics_partials(const float* pred, const float* gt, int B, int64_t HW, double* part, int nb,
                             hipStream_t st);
+// Offline evaluation (eval_kernels.hip): the twelve sums of DepthMetrics::compute per sample, {n, |d|/g,
+// d^2/g, d^2, dln^2, |d|, |dlog10|, a1, a2, a3, p, g}.  part: [B][nb][12] doubles (nb = eval_blocks(HW));
+// rows base .. base + B - 1 of table ([rows][12] doubles, device) receive the sums.  mask nullable.
+int eval_blocks(int64_t HW);
+void eval_update(const float* pred, const float* gt, const uint8_t* mask, int B, int64_t HW, float min_depth,
+                 float max_depth, int clamp_pred, double* part, int nb, double* table, int64_t base, hipStream_t st);
 void repack_conv_dgrad(const float* w, float* wd, int cout, int cin, hipStream_t st);
 void repack_convT_fwd(const float* wm, float* wf, int cin, int cout, hipStream_t st);
 // Per-step weight preparation in one launch (the weights change every step): a list of jobs, each

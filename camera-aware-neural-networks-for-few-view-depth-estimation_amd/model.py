@@ -366,6 +366,132 @@ def depth_metrics(pred: torch.Tensor, gt: torch.Tensor) -> dict:
     return {k: float(out[i]) for i, k in enumerate(keys)}
 
 
+EVAL_KEYS = _abi.EVAL_KEYS   # DepthMetrics::compute's keys, in cad.h's metric order
+
+
+class Evaluator:
+    """Device-resident table of DepthMetrics::compute's per-sample sums (cad_evaluator, cad.h).
+
+    update() enqueues two kernels on the current stream and returns: no allocation, no host
+    synchronisation.  sums() / metrics() / summary() make one synchronous copy of the table."""
+
+    def __init__(self, capacity, max_batch, H, W, min_depth=0.1, max_depth=10.0, clamp_pred=True, device=0):
+        self.lib = _abi.load()
+        self.device = torch.device("cuda", device)
+        self.capacity, self.max_batch, self.height, self.width = int(capacity), int(max_batch), int(H), int(W)
+        cfg = _abi.EvalConfig(min_depth, max_depth, int(bool(clamp_pred)))
+        h = C.c_void_p()
+        check(self.lib.cad_evaluator_create(self.capacity, self.max_batch, self.height, self.width, C.byref(cfg), device,
+                                            C.byref(h)), "cad_evaluator_create")
+        self.h = h
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.lib.cad_evaluator_destroy(h)
+            self.h = None
+
+    def update(self, pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | None = None):
+        """Append the B samples of pred / gt (B,1,H,W) [mask: (B,1,H,W), nonzero = valid]."""
+        B = pred.shape[0]
+        assert pred.numel() == gt.numel() == B * self.height * self.width, "pred / gt must be (B,1,H,W)"
+        m = None
+        if mask is not None:
+            assert mask.numel() == pred.numel(), "mask must be (B,1,H,W)"
+            mt = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else mask.to(torch.uint8).contiguous()
+            m = C.c_void_p(mt.data_ptr())
+        check(self.lib.cad_evaluator_update(self.h, _ptr(pred), _ptr(gt), m, B, _stream(self.device)),
+              "cad_evaluator_update")
+
+    def reset(self):
+        check(self.lib.cad_evaluator_reset(self.h), "cad_evaluator_reset")
+
+    @property
+    def count(self) -> int:
+        return int(self.lib.cad_evaluator_count(self.h))
+
+    def sums(self) -> np.ndarray:
+        """(count, 12) float64: {n, |d|/g, d^2/g, d^2, dln^2, |d|, |dlog10|, a1, a2, a3, p, g} sums."""
+        out = np.zeros((self.count, 12), np.float64)
+        check(self.lib.cad_evaluator_sums(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), _stream(self.device)),
+              "cad_evaluator_sums")
+        return out
+
+    def _finish(self):
+        per = np.zeros((self.count, 12), np.float32)
+        s = _abi.EvalSummary()
+        check(self.lib.cad_evaluator_metrics(self.h, per.ctypes.data_as(_abi.FP), C.byref(s)), "cad_evaluator_metrics")
+        return per, s
+
+    def metrics(self) -> np.ndarray:
+        """(count, 12) float32 per-sample metrics in EVAL_KEYS order (a sample without a valid pixel: zeros)."""
+        return self._finish()[0]
+
+    def summary(self) -> dict:
+        """{"count", "mean" | "std" | "median" | "min" | "max" | "pooled": {key: value}}."""
+        s = self._finish()[1]
+        out = {"count": int(s.count)}
+        for stat in ("mean", "std", "median", "min", "max", "pooled"):
+            out[stat] = {k: float(getattr(s, stat)[i]) for i, k in enumerate(EVAL_KEYS)}
+        return out
+
+
+def depth_metrics_full(pred, gt, mask=None, min_depth=0.1, max_depth=10.0, clamp_pred=True, per_sample=False):
+    """DepthMetrics::compute (src/evaluation/depth_metrics.h:40-88) of a batch: the twelve metrics over
+    all its valid pixels; per_sample=True: computePerSample (:93-117), a list of one dict per sample."""
+    B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
+    ev = Evaluator(B, B, H, W, min_depth, max_depth, clamp_pred, device=pred.device.index or 0)
+    ev.update(pred, gt, mask)
+    if per_sample:
+        return [{k: float(v) for k, v in zip(EVAL_KEYS, row)} for row in ev.metrics()]
+    return ev.summary()["pooled"]
+
+
+def _eval_forward(model, rgb, K):
+    if isinstance(model, GeometryAwareNetwork):
+        return model.forward(rgb, ray_directions(K, rgb.shape[2], rgb.shape[3]), camera_from_K(K))
+    if getattr(model, "conditioned", False):
+        return model.forward_cam(rgb, camera_from_K(K))
+    return model.forward(rgb)
+
+
+def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False):
+    """ModelEvaluator: eval-mode forwards over `batches` of (rgb, gt, K[, mask]) device tensors, every
+    prediction scored on device (Evaluator.update) with no host synchronisation inside the loop; the
+    model's train / eval mode is restored.  Returns {"keys", "per_sample" (N,12), "summary",
+    "forward_ms_per_image" (events around the whole loop), "parameters"[, "predictions"]}."""
+    batches = list(batches)
+    if not batches:
+        raise ValueError("evaluate: no batches")
+    H, W = batches[0][0].shape[2], batches[0][0].shape[3]
+    dev = batches[0][0].device
+    n = sum(int(b[0].shape[0]) for b in batches)
+    ev = Evaluator(n, max(int(b[0].shape[0]) for b in batches), H, W, min_depth, max_depth, clamp_pred,
+                   device=dev.index or 0)
+    was_training = bool(getattr(model, "training", True))
+    model.eval()
+    preds = []
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    try:
+        t0.record()
+        for b in batches:
+            rgb, gt, K = b[0], b[1], b[2]
+            pred = _eval_forward(model, rgb, K)
+            ev.update(pred, gt, b[3] if len(b) > 3 else None)
+            if keep_predictions:
+                preds.append(pred.clone())
+        t1.record()
+        per = ev.metrics()   # the first host-visible event: one copy of the table
+        ms = t0.elapsed_time(t1)
+    finally:
+        model.train(was_training)
+    out = {"keys": EVAL_KEYS, "per_sample": per, "summary": ev.summary(), "forward_ms_per_image": ms / n,
+           "parameters": model.count_parameters()}
+    if keep_predictions:
+        out["predictions"] = torch.cat(preds)
+    return out
+
+
 def ray_directions(K: torch.Tensor, height: int, width: int) -> torch.Tensor:
     """RayDirectionComputer::computeRayDirections for a batch of K (B,3,3) -> (B,3,H,W)."""
     lib = _abi.load()

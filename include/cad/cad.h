@@ -39,6 +39,14 @@
  *   cad_loss_forward_backward_masked forwardWithIntrinsics(pred, gt, image, K, valid_mask)
  *                                   depth_loss.h:416-433 with the optional mask
  *   cad_depth_metrics               computeDepthMetrics (abs_rel ...)          enhanced.h:400-439
+ *   cad_evaluator_create/destroy/reset/update/count/sums/metrics, cad_eval_finish
+ *                                   DepthMetrics::compute / computePerSample / average
+ *                                   src/evaluation/depth_metrics.h:40-141 (validity mask :147-164,
+ *                                   the metric formulas :169-233, getZeroMetrics :238-253) and the
+ *                                   mean / std / median of Evaluator::computeStatistics,
+ *                                   src/evaluation/evaluator.h:385-397, on a device-resident table of
+ *                                   per-sample sums (the reference's evaluation target does not build;
+ *                                   its metric definitions are the contract)
  *   cad_ray_directions              RayDirectionComputer::computeRayDirections
  *                                   src/preprocessing/ray_direction_computer.cpp:17-62
  *   cad_batcher_create/assemble     SunRGBDLoader::getSample's resizeSample + augmentSample
@@ -128,6 +136,13 @@ int cad_alias_views_overlap(const void* a, int64_t arows, int64_t ald, int64_t a
 cad_status cad_device_count(int* n);
 cad_status cad_set_device(int device);
 cad_status cad_stream_synchronize(void* stream);
+/* timing events for callers without HIP headers (the C++ evaluator's forward time): record on a stream;
+ * elapsed_ms waits for `stop` and returns the time between the two records */
+typedef struct cad_event cad_event;
+cad_status cad_event_create(cad_event** out);
+void cad_event_destroy(cad_event* ev);
+cad_status cad_event_record(cad_event* ev, void* stream);
+cad_status cad_event_elapsed_ms(cad_event* start, cad_event* stop, float* ms);
 /* device memory for callers without HIP headers (the C++ drop-in, the train CLI) */
 cad_status cad_malloc(int device, int64_t bytes, void** out);
 void cad_free(void* p);
@@ -312,6 +327,54 @@ cad_status cad_loss_get_components(cad_loss* l, float out5[5], void* stream);
 /* ---- metrics (computeDepthMetrics) on host-visible results: abs_rel etc. per sample, averaged */
 cad_status cad_depth_metrics(const float* pred, const float* gt, int B, int H, int W, float out7[7],
                              void* stream);
+
+/* ---- offline evaluation: DepthMetrics::compute (src/evaluation/depth_metrics.h:40-88) per sample over
+ * a whole split.  The evaluator owns a device table of `capacity` rows of twelve double sums
+ * {n, sum|p-g|/g, sum(p-g)^2/g, sum(p-g)^2, sum(ln p - ln g)^2, sum|p-g|, sum|log10 p - log10 g|,
+ *  #(r < 1.25), #(r < 1.25^2), #(r < 1.25^3), sum p, sum g},  r = max(p/g, g/p), over the valid pixels
+ * gt > min_depth && gt < max_depth (strict) [&& mask != 0], p = clamp(pred, min_depth, max_depth) when
+ * clamp_pred.  fp32 per-pixel terms, double accumulation in a fixed order: a sample's row is the same
+ * bits on every run, in whichever batch it arrives, from aligned or unaligned tensors.
+ * Metric order (CAD_EVAL_METRICS values per sample): abs_rel, sq_rel, rmse, rmse_log, mae, log10,
+ * delta_1.25, delta_1.25^2, delta_1.25^3, num_valid_pixels, mean_pred_depth, mean_gt_depth; a sample
+ * without a valid pixel yields twelve zeros and is counted (getZeroMetrics + average, :122-141,238). */
+#define CAD_EVAL_METRICS 12
+typedef struct {
+    float min_depth; /* 0.1 */
+    float max_depth; /* 10.0 */
+    int clamp_pred;  /* 1 */
+} cad_eval_config;
+typedef struct {
+    int64_t count;                   /* samples */
+    float mean[CAD_EVAL_METRICS];    /* over samples */
+    float std[CAD_EVAL_METRICS];     /* population standard deviation (/ N), evaluator.h:385-397 */
+    float median[CAD_EVAL_METRICS];  /* mean of the two middle values for even N */
+    float min[CAD_EVAL_METRICS];
+    float max[CAD_EVAL_METRICS];
+    float pooled[CAD_EVAL_METRICS];  /* the twelve sums added over all samples, finished once: what
+                                        DepthMetrics::compute returns for all samples as one batch */
+} cad_eval_summary;
+typedef struct cad_evaluator cad_evaluator;
+/* allocates everything the evaluator will ever need (table, partials for max_batch samples of H x W);
+ * cfg NULL: the defaults.  Arguments are checked before any device call. */
+cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, const cad_eval_config* cfg, int device,
+                                cad_evaluator** out);
+void cad_evaluator_destroy(cad_evaluator* e);
+cad_status cad_evaluator_reset(cad_evaluator* e); /* count = 0 (host counter only) */
+/* appends B rows: pred, gt (B,1,H,W) device fp32, mask (device, B*H*W bytes, nonzero = valid) or NULL.
+ * Two kernels on `stream`; no allocation, no host synchronisation, no host copy.  count + B > capacity
+ * or B > max_batch: CAD_ERR_INVALID, table and count unchanged.  Successive updates share the partials
+ * buffer: issue them on one stream (or order the streams yourself). */
+cad_status cad_evaluator_update(cad_evaluator* e, const float* pred, const float* gt, const uint8_t* mask, int B,
+                                void* stream);
+int64_t cad_evaluator_count(const cad_evaluator* e); /* samples so far */
+/* host copy of the table's first count rows (count x 12 doubles); one synchronous copy on `stream` */
+cad_status cad_evaluator_sums(cad_evaluator* e, double* out, void* stream);
+/* cad_evaluator_sums on the stream of the last update, then cad_eval_finish; per_sample may be NULL */
+cad_status cad_evaluator_metrics(cad_evaluator* e, float* per_sample, cad_eval_summary* s);
+/* host only (no device): n rows of twelve sums -> per-sample metrics (n x 12, nullable) and the summary
+ * (nullable), in double, rounded to fp32 at the end */
+cad_status cad_eval_finish(const double* sums, int64_t n, float* per_sample, cad_eval_summary* s);
 
 /* ---- conditioning: per-pixel unit ray directions (B,3,H,W) from K (B,3,3) ---- */
 cad_status cad_ray_directions(const float* K, int B, int H, int W, float* rays, void* stream);

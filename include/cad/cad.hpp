@@ -127,8 +127,12 @@ public:
         cad::check(cad_unet_backward(h_, ddepth.data, stream), "backward");
     }
     int64_t count_parameters() const { return cad_unet_count_parameters(h_); }
-    void train(bool on = true) { cad::check(cad_unet_train(h_, on ? 1 : 0), "train"); }
+    void train(bool on = true) {
+        cad::check(cad_unet_train(h_, on ? 1 : 0), "train");
+        training_ = on;
+    }
     void eval() { train(false); }
+    bool is_training() const { return training_; }   // Module::is_training(): train mode after construction
 
     std::vector<NamedTensor> named_parameters() const { return fetch(0); }
     std::vector<NamedTensor> named_buffers() const { return fetch(1); }
@@ -189,6 +193,7 @@ private:
     }
     cad::Workspace ws_;
     cad_unet* h_ = nullptr;
+    bool training_ = true;
 };
 
 // IntrinsicsConditionedUNetImpl(in, f, camera_dim = 4, max_depth)   (intrinsics_unet.h:137-270):
@@ -268,8 +273,12 @@ public:
         cad::check(cad_geonet_adam_step(h_, lr, beta1, beta2, eps, weight_decay, stream), "adam_step");
     }
     int64_t count_parameters() const { return cad_geonet_count_parameters(h_); }
-    void train(bool on = true) { cad::check(cad_geonet_train(h_, on ? 1 : 0), "train"); }
+    void train(bool on = true) {
+        cad::check(cad_geonet_train(h_, on ? 1 : 0), "train");
+        training_ = on;
+    }
     void eval() { train(false); }
+    bool is_training() const { return training_; }
     std::vector<NamedTensor> named_parameters() const { return fetch(0); }
     std::vector<NamedTensor> named_buffers() const { return fetch(1); }
     int load(const std::vector<NamedTensor>& ts) {
@@ -320,6 +329,7 @@ private:
     }
     cad::Workspace ws_;
     cad_geonet* h_ = nullptr;
+    bool training_ = true;
 };
 
 class LightweightGeometryNetworkImpl : public GeometryAwareNetworkImpl {

@@ -1,0 +1,316 @@
+// evaluator.hpp — header-only C++ drop-in for the reference's offline evaluation, over cad.hpp / cad.h.
+//
+//   camera_aware_depth::DepthMetricsFull    DepthMetrics            src/evaluation/depth_metrics.h:28-254
+//   camera_aware_depth::MetricsAccumulator  MetricsAccumulator      depth_metrics.h:259-304
+//   camera_aware_depth::formatMetrics       formatMetrics           depth_metrics.h:309-333
+//   camera_aware_depth::ModelEvaluator      Evaluator               src/evaluation/evaluator.h
+//
+// (cad.hpp's DepthMetrics struct is the trainer's seven-number computeDepthMetrics result; the evaluation
+// class therefore carries the name DepthMetricsFull.)  Everything is built on the device-resident
+// cad_evaluator: predictions are scored where they are produced, the twelve sums per sample stay on the
+// device, and one copy at the end brings them to the host.
+#ifndef CAD_EVALUATOR_HPP
+#define CAD_EVALUATOR_HPP
+
+#include <cstring>
+#include <fstream>
+#include <functional>
+#include <iomanip>
+#include <sstream>
+
+#include "cad.hpp"
+#include "trainer.hpp"
+
+namespace camera_aware_depth {
+
+using MetricMap = std::map<std::string, float>;
+
+// DepthMetrics::compute's keys in cad.h's metric order
+inline const std::array<const char*, CAD_EVAL_METRICS>& metricKeys() {
+    static const std::array<const char*, CAD_EVAL_METRICS> k = {
+        "abs_rel", "sq_rel", "rmse", "rmse_log", "mae", "log10", "delta_1.25", "delta_1.25^2", "delta_1.25^3",
+        "num_valid_pixels", "mean_pred_depth", "mean_gt_depth"};
+    return k;
+}
+inline MetricMap metricMap(const float* v) {
+    MetricMap m;
+    for (int k = 0; k < CAD_EVAL_METRICS; ++k) m[metricKeys()[(size_t)k]] = v[k];
+    return m;
+}
+
+// RAII handle of a cad_evaluator
+class MetricsTable {
+public:
+    MetricsTable(int64_t capacity, int max_batch, int H, int W, float min_depth = 0.1f, float max_depth = 10.0f,
+                 bool clamp_pred = true, int device = 0) {
+        const cad_eval_config c{min_depth, max_depth, clamp_pred ? 1 : 0};
+        cad::check(cad_evaluator_create(capacity, max_batch, H, W, &c, device, &h_), "cad_evaluator_create");
+    }
+    ~MetricsTable() { cad_evaluator_destroy(h_); }
+    MetricsTable(const MetricsTable&) = delete;
+    MetricsTable& operator=(const MetricsTable&) = delete;
+    // asynchronous on `stream`: no allocation, no host synchronisation
+    void update(const DeviceTensor& pred, const DeviceTensor& gt, const uint8_t* mask = nullptr, void* stream = nullptr) {
+        cad::check(cad_evaluator_update(h_, pred.data, gt.data, mask, (int)pred.size(0), stream), "cad_evaluator_update");
+    }
+    void reset() { cad::check(cad_evaluator_reset(h_), "cad_evaluator_reset"); }
+    int64_t count() const { return cad_evaluator_count(h_); }
+    // per-sample metrics (count x 12, metricKeys() order) and the summary; one synchronous copy
+    std::vector<float> metrics(cad_eval_summary* summary = nullptr) {
+        std::vector<float> per((size_t)count() * CAD_EVAL_METRICS);
+        cad::check(cad_evaluator_metrics(h_, per.data(), summary), "cad_evaluator_metrics");
+        return per;
+    }
+    cad_evaluator* handle() const { return h_; }
+
+private:
+    cad_evaluator* h_ = nullptr;
+};
+
+struct DepthMetricsFull {
+    // compute (depth_metrics.h:40-88): the metrics over all valid pixels of the batch
+    static MetricMap compute(const DeviceTensor& pred, const DeviceTensor& gt,
+                             const std::optional<cad::DeviceMask>& valid_mask = std::nullopt, float min_depth = 0.1f,
+                             float max_depth = 10.0f) {
+        cad_eval_summary s;
+        table(pred, gt, valid_mask, min_depth, max_depth, &s);
+        return metricMap(s.pooled);
+    }
+    // computePerSample (:93-117)
+    static std::vector<MetricMap> computePerSample(const DeviceTensor& pred, const DeviceTensor& gt,
+                                                   const std::optional<cad::DeviceMask>& valid_mask = std::nullopt,
+                                                   float min_depth = 0.1f, float max_depth = 10.0f) {
+        const std::vector<float> per = table(pred, gt, valid_mask, min_depth, max_depth, nullptr);
+        std::vector<MetricMap> out;
+        for (size_t i = 0; i < per.size(); i += CAD_EVAL_METRICS) out.push_back(metricMap(per.data() + i));
+        return out;
+    }
+    // average (:122-141)
+    static MetricMap average(const std::vector<MetricMap>& metrics_list) {
+        if (metrics_list.empty()) return getZeroMetrics();
+        MetricMap avg;
+        for (const auto& kv : metrics_list[0]) {
+            float sum = 0.0f;
+            for (const auto& m : metrics_list) sum += m.at(kv.first);
+            avg[kv.first] = sum / metrics_list.size();
+        }
+        return avg;
+    }
+    static MetricMap getZeroMetrics() {   // :238-253
+        const float z[CAD_EVAL_METRICS] = {0};
+        return metricMap(z);
+    }
+
+private:
+    static std::vector<float> table(const DeviceTensor& pred, const DeviceTensor& gt,
+                                    const std::optional<cad::DeviceMask>& mask, float min_depth, float max_depth,
+                                    cad_eval_summary* s) {
+        if (pred.numel() != gt.numel() || pred.dim() < 3) throw std::runtime_error("DepthMetrics: pred and gt must match");
+        if (mask && mask->numel() != pred.numel()) throw std::runtime_error("DepthMetrics: valid_mask must match pred");
+        const int B = (int)pred.size(0);
+        MetricsTable t(B, B, (int)pred.size(-2), (int)pred.size(-1), min_depth, max_depth, true, pred.device);
+        t.update(pred, gt, mask ? mask->data : nullptr);
+        return t.metrics(s);
+    }
+};
+
+class MetricsAccumulator {   // depth_metrics.h:259-304
+public:
+    void update(const MetricMap& metrics) {
+        for (const auto& kv : metrics) running_sum_[kv.first] += kv.second;
+        count_++;
+    }
+    MetricMap average() const {
+        MetricMap avg;
+        if (count_ == 0) return avg;
+        for (const auto& kv : running_sum_) avg[kv.first] = kv.second / count_;
+        return avg;
+    }
+    void reset() {
+        running_sum_.clear();
+        count_ = 0;
+    }
+    int64_t count() const { return count_; }
+
+private:
+    MetricMap running_sum_;
+    int64_t count_ = 0;
+};
+
+inline std::string formatMetrics(const MetricMap& m) {   // depth_metrics.h:309-333
+    std::stringstream ss;
+    ss << std::fixed << std::setprecision(4);
+    ss << "Error Metrics:\n";
+    ss << "  AbsRel:  " << m.at("abs_rel") << "\n";
+    ss << "  RMSE:    " << m.at("rmse") << "\n";
+    ss << "  RMSElog: " << m.at("rmse_log") << "\n";
+    ss << "  MAE:     " << m.at("mae") << "\n";
+    ss << "\nAccuracy Metrics (%):\n";
+    ss << "  δ < 1.25:    " << (m.at("delta_1.25") * 100.0f) << "%\n";
+    ss << "  δ < 1.25²:   " << (m.at("delta_1.25^2") * 100.0f) << "%\n";
+    ss << "  δ < 1.25³:   " << (m.at("delta_1.25^3") * 100.0f) << "%\n";
+    ss << "\nStatistics:\n";
+    ss << "  Valid pixels: " << static_cast<int>(m.at("num_valid_pixels")) << "\n";
+    ss << "  Mean pred:    " << m.at("mean_pred_depth") << "m\n";
+    ss << "  Mean GT:      " << m.at("mean_gt_depth") << "m\n";
+    return ss.str();
+}
+
+// the tensors of a .cadckpt file (trainer.hpp: named parameters and buffers in the reference layout; a
+// trailing optimizer section is ignored) into a model with load(std::vector<NamedTensor>)
+template <class Model>
+inline void load_model_state(const std::string& path, Model& m) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("Cannot open checkpoint: " + path);
+    char magic[8];
+    f.read(magic, 8);
+    if (!f || std::memcmp(magic, "CADCKPT1", 8) != 0) throw std::runtime_error("not a .cadckpt file: " + path);
+    int32_t n = 0;
+    f.read((char*)&n, 4);
+    if (!f || n < 0 || n > (1 << 20)) throw std::runtime_error("corrupt checkpoint: " + path);
+    std::vector<NamedTensor> ts((size_t)n);
+    for (auto& t : ts) {
+        int32_t ln = 0, nd = 0;
+        f.read((char*)&ln, 4);
+        if (!f || ln < 0 || ln > 4096) throw std::runtime_error("corrupt checkpoint: " + path);
+        t.name.resize((size_t)ln);
+        f.read(&t.name[0], ln);
+        f.read((char*)&nd, 4);
+        if (!f || nd < 0 || nd > 8) throw std::runtime_error("corrupt checkpoint: " + path);
+        t.shape.resize((size_t)nd);
+        f.read((char*)t.shape.data(), 8 * nd);
+        int64_t cnt = 1;
+        for (auto s : t.shape) cnt *= s;
+        if (!f || cnt < 0 || cnt > (int64_t(1) << 32)) throw std::runtime_error("corrupt checkpoint: " + path);
+        t.value.resize((size_t)cnt);
+        f.read((char*)t.value.data(), 4 * cnt);
+    }
+    if (!f || m.load(ts) != n) throw std::runtime_error("checkpoint does not match the model: " + path);
+}
+
+struct EvaluationConfig {
+    float min_depth = 0.1f;
+    float max_depth = 10.0f;
+    bool clamp_pred = true;
+    int batch_size = 8;
+    int device = 0;
+    int64_t max_samples = -1;   // -1: the whole loader
+    // called after each batch's update with (index of its first sample, predictions (n,1,H,W), n).  A
+    // callback that copies to the host synchronises; without one the loop never does.
+    std::function<void(int64_t, const DeviceTensor&, int)> on_batch;
+};
+
+struct EvaluationResult {
+    std::vector<MetricMap> sample_results;
+    std::vector<float> per_sample;   // count x 12, metricKeys() order
+    MetricMap mean_metrics, std_metrics, median_metrics, min_metrics, max_metrics, pooled_metrics;
+    double forward_ms_per_image = 0.0;   // HIP events around the whole loop / samples
+    int64_t num_parameters = 0;
+};
+
+class ModelEvaluator {
+public:
+    // BaselineUNetImpl and the camera-conditioned U-Nets derived from it (forward(x, intrinsics) from K)
+    ModelEvaluator(std::shared_ptr<BaselineUNetImpl> model, const EvaluationConfig& config) : config_(config) {
+        if (!model) throw std::runtime_error("ModelEvaluator: no model");
+        num_parameters_ = model->count_parameters();
+        set_mode_ = [model](bool train) { model->train(train); };
+        get_mode_ = [model] { return model->is_training(); };
+        forward_ = [model, this](int n) {
+            if (cad_unet_model(model->handle()) != CAD_MODEL_BASELINE) {
+                cad::check(cad_camera_from_K(K_.data, n, cam_.data, nullptr), "camera_from_K");
+                cad::check(cad_unet_forward_cam(model->handle(), rgb_.data, cam_.data, pred_.data, n, nullptr), "forward");
+            } else {
+                cad::check(cad_unet_forward(model->handle(), rgb_.data, pred_.data, n, nullptr), "forward");
+            }
+        };
+    }
+    // the geometry-aware networks: forward(rgb, rays(K), intrinsics(K)), as GeometryTrainer feeds them
+    ModelEvaluator(std::shared_ptr<GeometryAwareNetworkImpl> model, const EvaluationConfig& config) : config_(config) {
+        if (!model) throw std::runtime_error("ModelEvaluator: no model");
+        num_parameters_ = model->count_parameters();
+        set_mode_ = [model](bool train) { model->train(train); };
+        get_mode_ = [model] { return model->is_training(); };
+        forward_ = [model, this](int n) {
+            const int H = (int)rgb_.size(2), W = (int)rgb_.size(3);
+            if (rays_.numel() == 0) rays_ = DeviceTensor::empty({config_.batch_size, 3, H, W}, config_.device);
+            cad::check(cad_ray_directions(K_.data, n, H, W, rays_.data, nullptr), "rays");
+            cad::check(cad_camera_from_K(K_.data, n, cam_.data, nullptr), "camera_from_K");
+            cad::check(cad_geonet_forward(model->handle(), rgb_.data, rays_.data, cam_.data, pred_.data, n, nullptr),
+                       "forward");
+        };
+    }
+
+    ModelEvaluator(const ModelEvaluator&) = delete;
+    ModelEvaluator& operator=(const ModelEvaluator&) = delete;
+
+    // Eval-mode forwards over the loader's samples in order, batch by batch, each batch scored on the
+    // device; the model's previous train / eval mode is restored.
+    EvaluationResult evaluate(SunRGBDLoader& L) {
+        const bool restore_training = get_mode_();
+        const int B = config_.batch_size, H = L.target_height(), W = L.target_width(), d = config_.device;
+        int64_t ns = (int64_t)L.size();
+        if (config_.max_samples >= 0) ns = std::min(ns, config_.max_samples);
+        if (ns <= 0) throw std::runtime_error("ModelEvaluator: no samples");
+        rgb_ = DeviceTensor::empty({B, 3, H, W}, d);
+        gt_ = DeviceTensor::empty({B, 1, H, W}, d);
+        K_ = DeviceTensor::empty({B, 3, 3}, d);
+        pred_ = DeviceTensor::empty({B, 1, H, W}, d);
+        cam_ = DeviceTensor::empty({B, 4}, d);
+        rays_ = DeviceTensor();
+        MetricsTable table(ns, B, H, W, config_.min_depth, config_.max_depth, config_.clamp_pred, d);
+        cad_loader* ring = L.ring(B, d, false);
+        cad::check(cad_loader_start_epoch(ring, nullptr, ns), "evaluation");
+        cad_event *t0 = nullptr, *t1 = nullptr;
+        cad::check(cad_event_create(&t0), "event");
+        cad::check(cad_event_create(&t1), "event");
+        std::shared_ptr<cad_event> g0(t0, cad_event_destroy), g1(t1, cad_event_destroy);
+        set_mode_(false);
+        EvaluationResult r;
+        try {
+            cad::check(cad_event_record(t0, nullptr), "event");
+            for (int64_t first = 0;;) {
+                const int n = cad_loader_next(ring, rgb_.data, gt_.data, K_.data, nullptr);
+                if (n < 0) throw std::runtime_error(std::string("data loader: ") + cad_last_error());
+                if (n == 0) break;   // the loader's end of epoch: the loop's only host-visible event
+                for (DeviceTensor* t : {&rgb_, &gt_, &K_, &pred_, &cam_}) t->shape[0] = n;
+                forward_(n);
+                table.update(pred_, gt_);
+                if (config_.on_batch) config_.on_batch(first, pred_, n);
+                first += n;
+            }
+            cad::check(cad_event_record(t1, nullptr), "event");
+            cad_eval_summary s;
+            r.per_sample = table.metrics(&s);
+            float ms = 0.f;
+            cad::check(cad_event_elapsed_ms(t0, t1, &ms), "event");
+            r.forward_ms_per_image = (double)ms / (double)std::max<int64_t>(1, table.count());
+            for (size_t i = 0; i < r.per_sample.size(); i += CAD_EVAL_METRICS)
+                r.sample_results.push_back(metricMap(r.per_sample.data() + i));
+            r.mean_metrics = metricMap(s.mean);
+            r.std_metrics = metricMap(s.std);
+            r.median_metrics = metricMap(s.median);
+            r.min_metrics = metricMap(s.min);
+            r.max_metrics = metricMap(s.max);
+            r.pooled_metrics = metricMap(s.pooled);
+            r.num_parameters = num_parameters_;
+        } catch (...) {
+            set_mode_(restore_training);
+            throw;
+        }
+        set_mode_(restore_training);
+        return r;
+    }
+
+private:
+    EvaluationConfig config_;
+    int64_t num_parameters_ = 0;
+    std::function<void(bool)> set_mode_;
+    std::function<bool()> get_mode_;
+    std::function<void(int)> forward_;
+    DeviceTensor rgb_, gt_, K_, pred_, cam_, rays_;
+};
+
+}  // namespace camera_aware_depth
+
+#endif  // CAD_EVALUATOR_HPP
