@@ -61,6 +61,16 @@ EVAL_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "mae", "log10", "delta_1.2
              "num_valid_pixels", "mean_pred_depth", "mean_gt_depth")
 
 
+EVAL_ALIGN = {"none": 0, "median": 1, "log_mean": 2, "scale_shift": 3}   # cad_eval_align
+
+
+def eval_align_mode(align) -> int:
+    """cad_eval_align value of a mode name; ValueError for anything else (no device call)."""
+    if not isinstance(align, str) or align not in EVAL_ALIGN:
+        raise ValueError(f"align must be one of {tuple(EVAL_ALIGN)}, not {align!r}")
+    return EVAL_ALIGN[align]
+
+
 class EvalSummary(C.Structure):
     """cad_eval_summary (cad.h)."""
     _fields_ = [("count", I64)] + [(k, F * 12) for k in ("mean", "std", "median", "min", "max", "pooled")]
@@ -174,6 +184,12 @@ SIGNATURES = {
     "cad_evaluator_sums": (I, [P, C.POINTER(C.c_double), P]),
     "cad_evaluator_metrics": (I, [P, FP, C.POINTER(EvalSummary)]),
     "cad_eval_finish": (I, [C.POINTER(C.c_double), I64, FP, C.POINTER(EvalSummary)]),
+    "cad_evaluator_set_alignment": (I, [P, I]),
+    "cad_evaluator_get_alignment": (I, [P]),
+    "cad_evaluator_alignment": (I, [P, FP, P]),
+    "cad_evaluator_aligned": (I, [P, C.POINTER(C.c_uint8), P]),
+    "cad_valid_medians": (I, [P, P, P, I, I, I, F, F, P, P]),
+    "cad_eval_solve_alignment": (I, [I, C.POINTER(C.c_double), FP, FP]),
     "cad_ray_directions": (I, [P, I, I, I, P, P]),
     "cad_unet_debug_buffer": (I64, [P, C.c_char_p, FP, I64]),
     "cad_profile_enable": (I, [I]),

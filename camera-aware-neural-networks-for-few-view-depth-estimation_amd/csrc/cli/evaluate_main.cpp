@@ -4,6 +4,7 @@
 //
 //   build/evaluate -c <final_model.pt | .cadckpt> -g <train_config.yaml> [-o results/eval] [--data-dir D]
 //                  [--split val|train] [--save-predictions] [--gpu 0] [--dry-run]
+//                  [--align none|median|log_mean|scale_shift]
 //   build/evaluate --compare A/per_sample.csv B/per_sample.csv [--metric abs_rel] [--seed 42]
 //
 // The model (model.architecture, init_features, max_depth, variant, use_pcl, use_attention), the data
@@ -13,7 +14,11 @@
 // min(500, size) samples like validateEpoch and train all of them, both without augmentation.
 // Writes summary.csv, per_sample.csv, report.txt (the reference's report without its timing block, whose
 // per-image numbers need host timing around each forward) and, with --save-predictions, pred_<index>.npy
-// (fp32, H x W).  Any exception prints "Error: <what>" and exits 1, like build/train.
+// (fp32, H x W).  --align scores scale * pred + shift with a per-sample scale (median ratio, log mean or
+// least squares, computed on the device; cad.h "scale-aligned evaluation"): per_sample.csv then gains the
+// trailing columns scale, shift, aligned (0 where a fallback applied) and report.txt names the mode;
+// pred_<index>.npy stays the raw prediction, and with none every file is as without the flag.  Any
+// exception prints "Error: <what>" and exits 1, like build/train.
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
@@ -37,6 +42,7 @@ namespace {
 
 struct Args {
     std::string checkpoint, config, output = "results/eval", data_dir, split = "val", metric = "abs_rel";
+    Alignment align = Alignment::None;
     std::vector<std::string> compare;
     int gpu = 0;
     uint32_t seed = 42;
@@ -53,6 +59,8 @@ void usage() {
                  "      --save-predictions  Save every depth prediction as pred_<index>.npy\n"
                  "      --gpu arg         GPU ID (default: 0)\n"
                  "      --dry-run         Print the evaluation plan and exit; no GPU use\n"
+                 "      --align arg       Per-sample scale alignment before the metrics: none, median,\n"
+                 "                        log_mean or scale_shift (default: none)\n"
                  "      --compare A B     Paired comparison of two per_sample.csv files (no GPU use)\n"
                  "      --metric arg      Column compared by --compare (default: abs_rel)\n"
                  "      --seed arg        Bootstrap seed of --compare (default: 42)\n"
@@ -79,7 +87,11 @@ Args parse_args(int argc, char** argv) {
         else if (k == "--save-predictions") a.save_predictions = true;
         else if (k == "--gpu") a.gpu = std::stoi(next());
         else if (k == "--dry-run") a.dry_run = true;
-        else if (k == "--metric") a.metric = next();
+        else if (k == "--align") {
+            const std::string m = next();
+            if (!parseAlignment(m, &a.align))
+                throw std::runtime_error("--align '" + m + "': expected none, median, log_mean or scale_shift");
+        } else if (k == "--metric") a.metric = next();
         else if (k == "--seed") a.seed = (uint32_t)std::stoul(next());
         else if (k == "--compare") {
             a.compare.push_back(next());
@@ -193,15 +205,18 @@ void write_npy(const std::string& path, const float* data, int H, int W) {
 
 void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
     const auto& keys = metricKeys();
+    const bool al = a.align != Alignment::None;
     {
         std::ofstream f(a.output + "/per_sample.csv");
         if (!f) throw std::runtime_error("cannot write " + a.output + "/per_sample.csv");
         f << "index";
         for (const char* k : keys) f << "," << k;
+        if (al) f << ",scale,shift,aligned";
         f << "\n" << std::setprecision(9);
         for (size_t i = 0; i < r.sample_results.size(); ++i) {
             f << i;
             for (int k = 0; k < CAD_EVAL_METRICS; ++k) f << "," << r.per_sample[i * CAD_EVAL_METRICS + (size_t)k];
+            if (al) f << "," << r.alignment[2 * i] << "," << r.alignment[2 * i + 1] << "," << (int)r.aligned[i];
             f << "\n";
         }
     }
@@ -225,7 +240,21 @@ void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
     rep << "Model Type: " << c.architecture << (c.architecture == "geometry_aware" ? "/" + c.variant : std::string()) << "\n";
     rep << "Parameters: " << r.num_parameters << "\n";
     rep << "Test Samples: " << r.sample_results.size() << " (" << a.split << ")\n";
-    rep << "Evaluation Date: " << std::put_time(std::localtime(&now), "%Y-%m-%d %H:%M:%S") << "\n\n";
+    rep << "Evaluation Date: " << std::put_time(std::localtime(&now), "%Y-%m-%d %H:%M:%S") << "\n";
+    if (al) {
+        std::vector<double> sc;
+        int64_t fallbacks = 0;
+        for (size_t i = 0; i < r.aligned.size(); ++i) {
+            sc.push_back((double)r.alignment[2 * i]);
+            fallbacks += r.aligned[i] ? 0 : 1;
+        }
+        rep << "Alignment: " << alignmentName(a.align) << " (per sample; metrics score scale * pred + shift), scale "
+            << std::fixed << std::setprecision(4) << eval_stats::mean(sc) << " ± " << eval_stats::stddev(sc, 0) << ", "
+            << fallbacks << " fallback" << (fallbacks == 1 ? "" : "s") << "\n";
+        rep.unsetf(std::ios::floatfield);
+        rep << std::setprecision(6);
+    }
+    rep << "\n";
     rep << rule << "\n                    Performance Metrics\n" << rule << "\n\n";
     rep << std::fixed << std::setprecision(4);
     const auto pm = [&](const char* label, const char* k) {
@@ -287,7 +316,8 @@ int run(const Args& a) {
                   << "\", \"split\": \"" << a.split << "\", \"samples\": " << ns << ", \"batch_size\": " << c.batch_size
                   << ", \"batches\": " << (ns + c.batch_size - 1) / c.batch_size << ", \"height\": " << c.height
                   << ", \"width\": " << c.width << ", \"device\": " << a.gpu << ", \"output\": \"" << a.output
-                  << "\", \"save_predictions\": " << (a.save_predictions ? "true" : "false") << "}" << std::endl;
+                  << "\", \"save_predictions\": " << (a.save_predictions ? "true" : "false") << ", \"align\": \""
+                  << alignmentName(a.align) << "\"}" << std::endl;
         return 0;
     }
     int ndev = 0;
@@ -310,6 +340,7 @@ int run(const Args& a) {
     ec.batch_size = c.batch_size;
     ec.device = a.gpu;
     ec.max_samples = ns;
+    ec.align = a.align;
     if (a.save_predictions)
         ec.on_batch = [&](int64_t first, const DeviceTensor& pred, int n) {
             const std::vector<float> h = pred.to_host();
@@ -336,7 +367,8 @@ int run(const Args& a) {
     }
     std::cout << "Evaluating " << a.checkpoint << " (" << c.architecture << ", f=" << c.init_features << ") on " << ns << " "
               << a.split << " samples" << (real ? " of " + c.manifest_path : std::string(" (synthetic)")) << ", batch "
-              << c.batch_size << ", MI355X device " << a.gpu << "\n";
+              << c.batch_size << ", MI355X device " << a.gpu
+              << (a.align != Alignment::None ? std::string(", alignment ") + alignmentName(a.align) : std::string()) << "\n";
     const EvaluationResult r = ev->evaluate(*loader);
     write_outputs(a, c, r);
     std::cout << "\nMean over " << r.sample_results.size() << " samples:\n" << formatMetrics(r.mean_metrics) << "\nForward: "

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../../include/cad/cad.h"
+#include "../kernels/eval_align.hpp"
 #include "../kernels/kernels.hpp"
 
 namespace {
@@ -1745,6 +1746,12 @@ struct cad_evaluator {
     double* table = nullptr;   // [capacity][12]
     double* part = nullptr;    // [Bmax][nb][12]
     hipStream_t last = nullptr;
+    // scale alignment (cad_evaluator_set_alignment): one allocation, made at the first mode other than none
+    int align = CAD_ALIGN_NONE;
+    void* align_mem = nullptr;
+    float* align_table = nullptr;      // [capacity][2] {scale, shift}
+    uint8_t* align_flags = nullptr;    // [capacity], 0 where a fallback applied
+    cad::EvalAlignWs align_ws{};
 };
 
 cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, const cad_eval_config* cfg, int device,
@@ -1771,6 +1778,7 @@ cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, c
 void cad_evaluator_destroy(cad_evaluator* e) {
     if (!e) return;
     (void)hipFree(e->table);
+    if (e->align_mem) (void)hipFree(e->align_mem);
     delete e;
 }
 cad_status cad_evaluator_reset(cad_evaluator* e) {
@@ -1786,8 +1794,11 @@ cad_status cad_evaluator_update(cad_evaluator* e, const float* pred, const float
         require(B >= 1 && B <= e->Bmax, "batch exceeds the evaluator's max_batch");
         require(e->count + B <= e->capacity, "evaluator capacity exceeded");
         HIPCHK(hipSetDevice(e->device));
+        if (e->align != CAD_ALIGN_NONE)
+            cad::eval_align(e->align, pred, gt, mask, B, e->HW, e->cfg.min_depth, e->cfg.max_depth, e->align_ws, e->nb,
+                            e->align_table, e->align_flags, e->count, S(stream));
         cad::eval_update(pred, gt, mask, B, e->HW, e->cfg.min_depth, e->cfg.max_depth, e->cfg.clamp_pred, e->part, e->nb,
-                         e->table, e->count, S(stream));
+                         e->table, e->count, S(stream), e->align != CAD_ALIGN_NONE ? e->align_table : nullptr);
         HIPCHK(hipGetLastError());
         e->count += B;
         e->last = S(stream);
@@ -1867,6 +1878,87 @@ cad_status cad_evaluator_metrics(cad_evaluator* e, float* per_sample, cad_eval_s
         if (st != CAD_OK) return st;
     }
     return cad_eval_finish(sums.data(), e->count, per_sample, s);
+}
+
+// ---------------- scale-aligned evaluation ----------------
+cad_status cad_evaluator_set_alignment(cad_evaluator* e, int mode) {
+    return guard([&] {
+        require(e != nullptr, "null evaluator");
+        require(mode >= CAD_ALIGN_NONE && mode <= CAD_ALIGN_SCALE_SHIFT, "unknown alignment mode");
+        require(e->count == 0, "the alignment mode can only change while the evaluator is empty (count == 0)");
+        if (mode != CAD_ALIGN_NONE && !e->align_mem) {
+            HIPCHK(hipSetDevice(e->device));
+            const size_t wb = cad::eval_align_ws_bytes(e->Bmax, e->nb);
+            const size_t tb = (sizeof(float) * 2 * (size_t)e->capacity + 255) & ~(size_t)255;
+            void* mem = nullptr;
+            HIPCHK(hipMalloc(&mem, wb + tb + (size_t)e->capacity));
+            // the select needs zero bins whichever stream the first update uses: wait for the fill here
+            hipError_t err = hipMemset(mem, 0, wb + tb + (size_t)e->capacity);
+            if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+            if (err != hipSuccess) {
+                (void)hipFree(mem);
+                HIPCHK(err);
+            }
+            e->align_mem = mem;
+            e->align_ws = cad::eval_align_ws_carve(mem, e->Bmax, e->nb);
+            e->align_table = reinterpret_cast<float*>(static_cast<char*>(mem) + wb);
+            e->align_flags = reinterpret_cast<uint8_t*>(static_cast<char*>(mem) + wb + tb);
+        }
+        e->align = mode;
+    });
+}
+int cad_evaluator_get_alignment(const cad_evaluator* e) { return e ? e->align : CAD_ALIGN_NONE; }
+cad_status cad_evaluator_alignment(cad_evaluator* e, float* out, void* stream) {
+    return guard([&] {
+        require(e && out, "null argument");
+        if (e->count == 0) return;
+        if (e->align == CAD_ALIGN_NONE) {
+            for (int64_t i = 0; i < e->count; ++i) { out[2 * i] = 1.0f; out[2 * i + 1] = 0.0f; }
+            return;
+        }
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipMemcpyAsync(out, e->align_table, sizeof(float) * 2 * (size_t)e->count, hipMemcpyDeviceToHost, S(stream)));
+        HIPCHK(hipStreamSynchronize(S(stream)));
+    });
+}
+cad_status cad_evaluator_aligned(cad_evaluator* e, uint8_t* out, void* stream) {
+    return guard([&] {
+        require(e && out, "null argument");
+        if (e->count == 0) return;
+        if (e->align == CAD_ALIGN_NONE) {
+            std::memset(out, 0, (size_t)e->count);
+            return;
+        }
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipMemcpyAsync(out, e->align_flags, (size_t)e->count, hipMemcpyDeviceToHost, S(stream)));
+        HIPCHK(hipStreamSynchronize(S(stream)));
+    });
+}
+cad_status cad_valid_medians(const float* pred, const float* gt, const uint8_t* mask, int B, int H, int W, float min_depth,
+                             float max_depth, float* out, void* stream) {
+    return guard([&] {
+        require(pred && gt && out, "null argument");
+        require(B > 0 && H > 0 && W > 0, "valid_medians: B, H and W must be positive");
+        require(min_depth > 0.f && min_depth < max_depth, "valid_medians needs 0 < min_depth < max_depth");
+        const int64_t HW = (int64_t)H * W;
+        const int nb = cad::eval_blocks(HW);
+        const size_t wb = cad::eval_align_ws_bytes(B, nb);
+        void* mem = nullptr;
+        HIPCHK(hipMalloc(&mem, wb));
+        std::shared_ptr<void> hold(mem, [](void* p) { (void)hipFree(p); });
+        HIPCHK(hipMemsetAsync(mem, 0, wb, S(stream)));
+        cad::eval_valid_medians(pred, gt, mask, B, HW, min_depth, max_depth, cad::eval_align_ws_carve(mem, B, nb), nb, out,
+                                S(stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(S(stream)));
+    });
+}
+cad_status cad_eval_solve_alignment(int mode, const double stats[7], const float med[2], float out2[2]) {
+    return guard([&] {
+        require(mode >= CAD_ALIGN_NONE && mode <= CAD_ALIGN_SCALE_SHIFT, "unknown alignment mode");
+        require(stats && out2 && (med || mode != CAD_ALIGN_MEDIAN), "null argument");
+        cad::eval_solve_alignment(mode, stats, med, out2);
+    });
 }
 
 cad_status cad_camera_from_K(const float* K, int B, float* cam4, void* stream) {

@@ -2,7 +2,8 @@
 // (src/evaluation/depth_metrics.h:40-88, 147-233) in one pass over pred / gt / mask.
 //
 //   valid   gt > min_depth && gt < max_depth (both strict) [&& mask != 0]        (:154-161)
-//   p       clamp(pred, min_depth, max_depth) when clamp_pred                     (:66)
+//   p       clamp(pred, min_depth, max_depth) when clamp_pred                     (:66); with a scale
+//           alignment (eval_align_kernels.hip) the clamp is applied to scale * pred + shift
 //   sums    {n, |p-g|/g, (p-g)^2/g, (p-g)^2, (ln p - ln g)^2, |p-g|, |log10 p - log10 g|,
 //            #(r < 1.25), #(r < 1.25^2), #(r < 1.25^3), p, g},  r = max(p/g, g/p)  (:169-233)
 //
@@ -54,12 +55,27 @@ __device__ __forceinline__ void eval_pixel(EvalAcc& a, float pr, float g, bool m
     a.v[11] += (double)g;
 }
 
+// scale * pred + shift of an aligned evaluation: one fp32 multiply and one fp32 add
+__device__ __forceinline__ float align_pred(float pr, float s, float t) {
+#pragma clang fp contract(off)
+    const float m = s * pr;
+    return m + t;
+}
+
 // grid (nb, B), 256 threads.  VEC: HW % 4 == 0 and 16-byte (mask: 4-byte) aligned sample bases.
-template <bool VEC>
+// ALIGN: score scale * pred + shift with the sample's row of `align` ([rows][2], row base + b).
+template <bool VEC, bool ALIGN>
 __global__ __launch_bounds__(kEvalThreads) void k_eval_partials(const float* __restrict__ pred, const float* __restrict__ gt,
                                                                 const uint8_t* __restrict__ mask, int64_t HW, float lo,
-                                                                float hi, int clamp_pred, double* __restrict__ part, int nb) {
+                                                                float hi, int clamp_pred, double* __restrict__ part, int nb,
+                                                                const float* __restrict__ align, int64_t base) {
     const int b = blockIdx.y;
+    float as = 1.f, at = 0.f;
+    if constexpr (ALIGN) {
+        as = align[(base + b) * 2];
+        at = align[(base + b) * 2 + 1];
+    }
+    const auto ap = [&](float pr) { return ALIGN ? align_pred(pr, as, at) : pr; };
     const float* ps = pred + (int64_t)b * HW;
     const float* gs = gt + (int64_t)b * HW;
     const uint8_t* ms = mask ? mask + (int64_t)b * HW : nullptr;
@@ -73,13 +89,13 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_partials(const float* __r
             const float4 g4 = *reinterpret_cast<const float4*>(gs + i);
             uchar4 m4 = make_uchar4(1, 1, 1, 1);
             if (ms) m4 = *reinterpret_cast<const uchar4*>(ms + i);
-            eval_pixel(a, p4.x, g4.x, m4.x != 0, lo, hi, clamp_pred);
-            eval_pixel(a, p4.y, g4.y, m4.y != 0, lo, hi, clamp_pred);
-            eval_pixel(a, p4.z, g4.z, m4.z != 0, lo, hi, clamp_pred);
-            eval_pixel(a, p4.w, g4.w, m4.w != 0, lo, hi, clamp_pred);
+            eval_pixel(a, ap(p4.x), g4.x, m4.x != 0, lo, hi, clamp_pred);
+            eval_pixel(a, ap(p4.y), g4.y, m4.y != 0, lo, hi, clamp_pred);
+            eval_pixel(a, ap(p4.z), g4.z, m4.z != 0, lo, hi, clamp_pred);
+            eval_pixel(a, ap(p4.w), g4.w, m4.w != 0, lo, hi, clamp_pred);
         } else {
             const int n = (int)(HW - i < 4 ? HW - i : 4);   // the last quad may be short
-            for (int j = 0; j < n; ++j) eval_pixel(a, ps[i + j], gs[i + j], ms ? ms[i + j] != 0 : true, lo, hi, clamp_pred);
+            for (int j = 0; j < n; ++j) eval_pixel(a, ap(ps[i + j]), gs[i + j], ms ? ms[i + j] != 0 : true, lo, hi, clamp_pred);
         }
     }
     __shared__ double red[kEvalThreads / 64][kEvalSums];
@@ -112,15 +128,16 @@ int eval_blocks(int64_t HW) {
 }
 
 void eval_update(const float* pred, const float* gt, const uint8_t* mask, int B, int64_t HW, float min_depth,
-                 float max_depth, int clamp_pred, double* part, int nb, double* table, int64_t base, hipStream_t st) {
+                 float max_depth, int clamp_pred, double* part, int nb, double* table, int64_t base, hipStream_t st,
+                 const float* align) {
     const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(pred) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(gt) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
-    if (vec)
-        hipLaunchKernelGGL(k_eval_partials<true>, dim3(nb, B), dim3(kEvalThreads), 0, st, pred, gt, mask, HW, min_depth,
-                           max_depth, clamp_pred, part, nb);
-    else
-        hipLaunchKernelGGL(k_eval_partials<false>, dim3(nb, B), dim3(kEvalThreads), 0, st, pred, gt, mask, HW, min_depth,
-                           max_depth, clamp_pred, part, nb);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nb, B), dim3(kEvalThreads), 0, st, pred, gt, mask, HW, min_depth, max_depth, clamp_pred,
+                           part, nb, align, base);
+    };
+    if (align) vec ? launch(k_eval_partials<true, true>) : launch(k_eval_partials<false, true>);
+    else vec ? launch(k_eval_partials<true, false>) : launch(k_eval_partials<false, false>);
     hipLaunchKernelGGL(k_eval_final, dim3(B), dim3(64), 0, st, part, nb, table, base);
 }
 

@@ -309,7 +309,27 @@ void depth_metrics_partials(const float* pred, const float* gt, int B, int64_t H
 // rows base .. base + B - 1 of table ([rows][12] doubles, device) receive the sums.  mask nullable.
 int eval_blocks(int64_t HW);
 void eval_update(const float* pred, const float* gt, const uint8_t* mask, int B, int64_t HW, float min_depth,
-                 float max_depth, int clamp_pred, double* part, int nb, double* table, int64_t base, hipStream_t st);
+                 float max_depth, int clamp_pred, double* part, int nb, double* table, int64_t base, hipStream_t st,
+                 const float* align = nullptr);
+// Scale alignment of the evaluation (eval_align_kernels.hip; the closed forms are in eval_align.hpp).
+// eval_align writes rows base .. base + B - 1 of `table` ([rows][2] floats {scale, shift}) and of `flags`
+// ([rows] bytes, 0 where a fallback applied) for mode 1 (median: radix select), 2 (log mean) or 3 (least
+// squares); eval_update then scores scale * pred + shift when given that table.  The workspace holds
+// max_batch samples and must be zero when first used (the select leaves its bins zero again).
+struct EvalAlignWs {
+    double* part;     // [B][nb][7] statistics partials
+    double* stats;    // [B][7]
+    unsigned* hist;   // [B][4][256] radix-select bins
+    unsigned* sel;    // [B][12] selector state
+    float* med;       // [B][2] {med_pred, med_gt}
+};
+size_t eval_align_ws_bytes(int max_batch, int nb);
+EvalAlignWs eval_align_ws_carve(void* base, int max_batch, int nb);
+// medians of pred and gt over each sample's valid pixels -> med ([B][2], {0, 0} without a valid pixel)
+void eval_valid_medians(const float* pred, const float* gt, const uint8_t* mask, int B, int64_t HW, float min_depth,
+                        float max_depth, const EvalAlignWs& ws, int nb, float* med, hipStream_t st);
+void eval_align(int mode, const float* pred, const float* gt, const uint8_t* mask, int B, int64_t HW, float min_depth,
+                float max_depth, const EvalAlignWs& ws, int nb, float* table, uint8_t* flags, int64_t base, hipStream_t st);
 void repack_conv_dgrad(const float* w, float* wd, int cout, int cin, hipStream_t st);
 void repack_convT_fwd(const float* wm, float* wf, int cin, int cout, hipStream_t st);
 // Per-step weight preparation in one launch (the weights change every step): a list of jobs, each

@@ -372,10 +372,16 @@ EVAL_KEYS = _abi.EVAL_KEYS   # DepthMetrics::compute's keys, in cad.h's metric o
 class Evaluator:
     """Device-resident table of DepthMetrics::compute's per-sample sums (cad_evaluator, cad.h).
 
-    update() enqueues two kernels on the current stream and returns: no allocation, no host
-    synchronisation.  sums() / metrics() / summary() make one synchronous copy of the table."""
+    update() enqueues its kernels on the current stream and returns: no allocation, no host
+    synchronisation.  sums() / metrics() / summary() make one synchronous copy of the table.
 
-    def __init__(self, capacity, max_batch, H, W, min_depth=0.1, max_depth=10.0, clamp_pred=True, device=0):
+    align: "none" | "median" | "log_mean" | "scale_shift" — a per-sample (scale, shift) computed on the
+    device from the valid pixels (cad.h, "scale-aligned evaluation"); the metrics then score
+    scale * pred + shift.  alignment() returns the (scale, shift) rows."""
+
+    def __init__(self, capacity, max_batch, H, W, min_depth=0.1, max_depth=10.0, clamp_pred=True, device=0,
+                 align="none"):
+        mode = _abi.eval_align_mode(align)
         self.lib = _abi.load()
         self.device = torch.device("cuda", device)
         self.capacity, self.max_batch, self.height, self.width = int(capacity), int(max_batch), int(H), int(W)
@@ -384,6 +390,8 @@ class Evaluator:
         check(self.lib.cad_evaluator_create(self.capacity, self.max_batch, self.height, self.width, C.byref(cfg), device,
                                             C.byref(h)), "cad_evaluator_create")
         self.h = h
+        if mode:
+            check(self.lib.cad_evaluator_set_alignment(self.h, mode), "cad_evaluator_set_alignment")
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -405,6 +413,29 @@ class Evaluator:
 
     def reset(self):
         check(self.lib.cad_evaluator_reset(self.h), "cad_evaluator_reset")
+
+    def set_alignment(self, align):
+        """Change the alignment mode; allowed only while count == 0 (CadError otherwise)."""
+        check(self.lib.cad_evaluator_set_alignment(self.h, _abi.eval_align_mode(align)), "cad_evaluator_set_alignment")
+
+    @property
+    def align(self) -> str:
+        mode = int(self.lib.cad_evaluator_get_alignment(self.h))
+        return next(k for k, v in _abi.EVAL_ALIGN.items() if v == mode)
+
+    def alignment(self) -> np.ndarray:
+        """(count, 2) float32: the (scale, shift) of every sample; (1, 0) rows with align="none"."""
+        out = np.zeros((self.count, 2), np.float32)
+        check(self.lib.cad_evaluator_alignment(self.h, out.ctypes.data_as(_abi.FP), _stream(self.device)),
+              "cad_evaluator_alignment")
+        return out
+
+    def aligned(self) -> np.ndarray:
+        """(count,) bool: False where a fallback gave the sample's (scale, shift) (all False with "none")."""
+        out = np.zeros((self.count,), np.uint8)
+        check(self.lib.cad_evaluator_aligned(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8)), _stream(self.device)),
+              "cad_evaluator_aligned")
+        return out.astype(bool)
 
     @property
     def count(self) -> int:
@@ -436,15 +467,36 @@ class Evaluator:
         return out
 
 
-def depth_metrics_full(pred, gt, mask=None, min_depth=0.1, max_depth=10.0, clamp_pred=True, per_sample=False):
+def depth_metrics_full(pred, gt, mask=None, min_depth=0.1, max_depth=10.0, clamp_pred=True, per_sample=False,
+                       align="none"):
     """DepthMetrics::compute (src/evaluation/depth_metrics.h:40-88) of a batch: the twelve metrics over
-    all its valid pixels; per_sample=True: computePerSample (:93-117), a list of one dict per sample."""
+    all its valid pixels; per_sample=True: computePerSample (:93-117), a list of one dict per sample.
+    align: each sample's prediction is scale-aligned first (Evaluator)."""
+    _abi.eval_align_mode(align)
     B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
-    ev = Evaluator(B, B, H, W, min_depth, max_depth, clamp_pred, device=pred.device.index or 0)
+    ev = Evaluator(B, B, H, W, min_depth, max_depth, clamp_pred, device=pred.device.index or 0, align=align)
     ev.update(pred, gt, mask)
     if per_sample:
         return [{k: float(v) for k, v in zip(EVAL_KEYS, row)} for row in ev.metrics()]
     return ev.summary()["pooled"]
+
+
+def valid_medians(pred, gt, mask=None, min_depth=0.1, max_depth=10.0) -> torch.Tensor:
+    """(B, 2) device tensor {median of pred, median of gt} over each sample's valid pixels (gt strictly
+    inside (min_depth, max_depth) [and mask != 0]); exact (np.median of the float32 values), computed on
+    the device by radix select.  A sample without a valid pixel gives (0, 0)."""
+    lib = _abi.load()
+    B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
+    assert pred.numel() == gt.numel() == B * H * W, "pred / gt must be (B,1,H,W)"
+    m = None
+    if mask is not None:
+        assert mask.numel() == pred.numel(), "mask must be (B,1,H,W)"
+        mt = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else mask.to(torch.uint8).contiguous()
+        m = C.c_void_p(mt.data_ptr())
+    out = torch.empty((B, 2), dtype=torch.float32, device=pred.device)
+    check(lib.cad_valid_medians(_ptr(pred), _ptr(gt), m, B, H, W, min_depth, max_depth, _ptr(out), _stream(pred.device)),
+          "cad_valid_medians")
+    return out
 
 
 def _eval_forward(model, rgb, K):
@@ -455,11 +507,13 @@ def _eval_forward(model, rgb, K):
     return model.forward(rgb)
 
 
-def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False):
+def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False, align="none"):
     """ModelEvaluator: eval-mode forwards over `batches` of (rgb, gt, K[, mask]) device tensors, every
     prediction scored on device (Evaluator.update) with no host synchronisation inside the loop; the
     model's train / eval mode is restored.  Returns {"keys", "per_sample" (N,12), "summary",
-    "forward_ms_per_image" (events around the whole loop), "parameters"[, "predictions"]}."""
+    "forward_ms_per_image" (events around the whole loop), "parameters", "align", "alignment" (N,2)
+    (scale, shift) per sample[, "predictions" (the raw ones)]}."""
+    _abi.eval_align_mode(align)
     batches = list(batches)
     if not batches:
         raise ValueError("evaluate: no batches")
@@ -467,7 +521,7 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
     dev = batches[0][0].device
     n = sum(int(b[0].shape[0]) for b in batches)
     ev = Evaluator(n, max(int(b[0].shape[0]) for b in batches), H, W, min_depth, max_depth, clamp_pred,
-                   device=dev.index or 0)
+                   device=dev.index or 0, align=align)
     was_training = bool(getattr(model, "training", True))
     model.eval()
     preds = []
@@ -486,7 +540,7 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
     finally:
         model.train(was_training)
     out = {"keys": EVAL_KEYS, "per_sample": per, "summary": ev.summary(), "forward_ms_per_image": ms / n,
-           "parameters": model.count_parameters()}
+           "parameters": model.count_parameters(), "align": align, "alignment": ev.alignment()}
     if keep_predictions:
         out["predictions"] = torch.cat(preds)
     return out

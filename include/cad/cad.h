@@ -47,6 +47,10 @@
  *                                   src/evaluation/evaluator.h:385-397, on a device-resident table of
  *                                   per-sample sums (the reference's evaluation target does not build;
  *                                   its metric definitions are the contract)
+ *   cad_evaluator_set_alignment/get_alignment/alignment/aligned, cad_valid_medians,
+ *   cad_eval_solve_alignment        per-sample median / log-mean / least-squares alignment of the
+ *                                   prediction before the metrics (new: no reference counterpart; the
+ *                                   reference scores raw predictions only)
  *   cad_ray_directions              RayDirectionComputer::computeRayDirections
  *                                   src/preprocessing/ray_direction_computer.cpp:17-62
  *   cad_batcher_create/assemble     SunRGBDLoader::getSample's resizeSample + augmentSample
@@ -362,7 +366,8 @@ cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, c
 void cad_evaluator_destroy(cad_evaluator* e);
 cad_status cad_evaluator_reset(cad_evaluator* e); /* count = 0 (host counter only) */
 /* appends B rows: pred, gt (B,1,H,W) device fp32, mask (device, B*H*W bytes, nonzero = valid) or NULL.
- * Two kernels on `stream`; no allocation, no host synchronisation, no host copy.  count + B > capacity
+ * Two kernels on `stream` (the alignment kernels before them with an alignment mode, below); no allocation,
+ * no host synchronisation, no host copy.  count + B > capacity
  * or B > max_batch: CAD_ERR_INVALID, table and count unchanged.  Successive updates share the partials
  * buffer: issue them on one stream (or order the streams yourself). */
 cad_status cad_evaluator_update(cad_evaluator* e, const float* pred, const float* gt, const uint8_t* mask, int B,
@@ -375,6 +380,40 @@ cad_status cad_evaluator_metrics(cad_evaluator* e, float* per_sample, cad_eval_s
 /* host only (no device): n rows of twelve sums -> per-sample metrics (n x 12, nullable) and the summary
  * (nullable), in double, rounded to fp32 at the end */
 cad_status cad_eval_finish(const double* sums, int64_t n, float* per_sample, cad_eval_summary* s);
+
+/* ---- scale-aligned evaluation.  With an alignment mode set, update first computes a per-sample
+ * (scale s, shift t) on the device, stores it in a table of capacity x 2 floats, and the metrics pass
+ * scores s * pred + t (one fp32 multiply, one fp32 add, then the clamp_pred clamp).  The statistics run
+ * over the evaluator's valid pixels and use the raw pred, before the clamp; finite pred is a precondition.
+ *   CAD_ALIGN_NONE         s = 1, t = 0: the unaligned code path, bit-identical rows
+ *   CAD_ALIGN_MEDIAN       s = med(gt) / med(pred) as one fp32 division; med(v) = (v_sorted[(n-1)/2] +
+ *                          v_sorted[n/2]) * 0.5f in fp32, found exactly by radix select on the device
+ *   CAD_ALIGN_LOG_MEAN     s = exp(mean(ln gt - ln pred)) over the valid pixels with pred > 0 (double)
+ *   CAD_ALIGN_SCALE_SHIFT  the (s, t) minimising sum (s pred + t - gt)^2, closed form in double from
+ *                          n, sum p, sum g, sum p^2, sum pg
+ * Fallbacks: no valid pixel, med(pred) <= 0, or no valid pixel with pred > 0: (1, 0); scale_shift with
+ * n sum p^2 - (sum p)^2 <= 0: scale only, s = sum pg / sum p^2 (1 when sum p^2 = 0), t = 0.  A sample's
+ * (s, t) is the same bits on every run, in whichever batch it arrives, from aligned or unaligned tensors. */
+typedef enum { CAD_ALIGN_NONE = 0, CAD_ALIGN_MEDIAN = 1, CAD_ALIGN_LOG_MEAN = 2, CAD_ALIGN_SCALE_SHIFT = 3 } cad_eval_align;
+/* allowed only while count == 0 (after create or reset); allocates the alignment workspace here, so that
+ * update still allocates nothing.  Unknown mode or count > 0: CAD_ERR_INVALID, nothing changed. */
+cad_status cad_evaluator_set_alignment(cad_evaluator* e, int mode);
+int cad_evaluator_get_alignment(const cad_evaluator* e);
+/* host copy of the first count rows of (scale, shift): count x 2 floats, one synchronous copy on `stream`
+ * ((1, 0) rows with CAD_ALIGN_NONE, without a device call) */
+cad_status cad_evaluator_alignment(cad_evaluator* e, float* out, void* stream);
+/* count bytes beside cad_evaluator_alignment: 1 where the mode's own formula gave the row, 0 where a
+ * fallback applied (all 0 with CAD_ALIGN_NONE) */
+cad_status cad_evaluator_aligned(cad_evaluator* e, uint8_t* out, void* stream);
+/* stand-alone: medians of pred and gt over each sample's valid pixels -> out (device, B x 2 floats
+ * {med_pred, med_gt}; 0, 0 without a valid pixel).  Allocates and frees its own workspace and waits for
+ * `stream`.  Arguments are checked before any device call. */
+cad_status cad_valid_medians(const float* pred, const float* gt, const uint8_t* mask, int B, int H, int W,
+                             float min_depth, float max_depth, float* out, void* stream);
+/* host only (no device): stats = {n, n_pos, sum p, sum g, sum p^2, sum pg, sum(ln g - ln p)},
+ * med = {med_pred, med_gt} (read for CAD_ALIGN_MEDIAN only, may be NULL otherwise) -> out2 = {scale, shift}.
+ * The code the device solve kernel runs. */
+cad_status cad_eval_solve_alignment(int mode, const double stats[7], const float med[2], float out2[2]);
 
 /* ---- conditioning: per-pixel unit ray directions (B,3,H,W) from K (B,3,3) ---- */
 cad_status cad_ray_directions(const float* K, int B, int H, int W, float* rays, void* stream);

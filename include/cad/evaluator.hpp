@@ -38,13 +38,39 @@ inline MetricMap metricMap(const float* v) {
     return m;
 }
 
+// per-sample scale alignment of the prediction before the metrics (cad_eval_align of cad.h; the reference
+// has no counterpart)
+enum class Alignment { None = CAD_ALIGN_NONE, Median = CAD_ALIGN_MEDIAN, LogMean = CAD_ALIGN_LOG_MEAN,
+                       ScaleShift = CAD_ALIGN_SCALE_SHIFT };
+inline const char* alignmentName(Alignment a) {
+    switch (a) {
+        case Alignment::Median: return "median";
+        case Alignment::LogMean: return "log_mean";
+        case Alignment::ScaleShift: return "scale_shift";
+        default: return "none";
+    }
+}
+inline bool parseAlignment(const std::string& s, Alignment* out) {
+    for (Alignment a : {Alignment::None, Alignment::Median, Alignment::LogMean, Alignment::ScaleShift})
+        if (s == alignmentName(a)) {
+            *out = a;
+            return true;
+        }
+    return false;
+}
+
 // RAII handle of a cad_evaluator
 class MetricsTable {
 public:
     MetricsTable(int64_t capacity, int max_batch, int H, int W, float min_depth = 0.1f, float max_depth = 10.0f,
-                 bool clamp_pred = true, int device = 0) {
+                 bool clamp_pred = true, int device = 0, Alignment align = Alignment::None) {
         const cad_eval_config c{min_depth, max_depth, clamp_pred ? 1 : 0};
         cad::check(cad_evaluator_create(capacity, max_batch, H, W, &c, device, &h_), "cad_evaluator_create");
+        if (align != Alignment::None && cad_evaluator_set_alignment(h_, (int)align) != CAD_OK) {
+            const std::string why = cad_last_error();
+            cad_evaluator_destroy(h_);
+            throw std::runtime_error("cad_evaluator_set_alignment: " + why);
+        }
     }
     ~MetricsTable() { cad_evaluator_destroy(h_); }
     MetricsTable(const MetricsTable&) = delete;
@@ -60,6 +86,20 @@ public:
         std::vector<float> per((size_t)count() * CAD_EVAL_METRICS);
         cad::check(cad_evaluator_metrics(h_, per.data(), summary), "cad_evaluator_metrics");
         return per;
+    }
+    // allowed only while count() == 0
+    void setAlignment(Alignment a) { cad::check(cad_evaluator_set_alignment(h_, (int)a), "cad_evaluator_set_alignment"); }
+    Alignment alignmentMode() const { return (Alignment)cad_evaluator_get_alignment(h_); }
+    // per-sample (scale, shift), count x 2, and (nullable) whether the mode's own formula gave the row
+    // (0 where a fallback applied); synchronous copies on the stream of the caller's updates
+    std::vector<float> alignment(std::vector<uint8_t>* aligned = nullptr, void* stream = nullptr) {
+        std::vector<float> st((size_t)count() * 2);
+        cad::check(cad_evaluator_alignment(h_, st.data(), stream), "cad_evaluator_alignment");
+        if (aligned) {
+            aligned->assign((size_t)count(), 0);
+            cad::check(cad_evaluator_aligned(h_, aligned->data(), stream), "cad_evaluator_aligned");
+        }
+        return st;
     }
     cad_evaluator* handle() const { return h_; }
 
@@ -192,6 +232,7 @@ struct EvaluationConfig {
     float min_depth = 0.1f;
     float max_depth = 10.0f;
     bool clamp_pred = true;
+    Alignment align = Alignment::None;   // per-sample scale alignment before the metrics
     int batch_size = 8;
     int device = 0;
     int64_t max_samples = -1;   // -1: the whole loader
@@ -203,6 +244,9 @@ struct EvaluationConfig {
 struct EvaluationResult {
     std::vector<MetricMap> sample_results;
     std::vector<float> per_sample;   // count x 12, metricKeys() order
+    Alignment align = Alignment::None;
+    std::vector<float> alignment;    // count x 2 (scale, shift); (1, 0) rows without alignment
+    std::vector<uint8_t> aligned;    // count; 0 where a fallback gave the row (all 0 without alignment)
     MetricMap mean_metrics, std_metrics, median_metrics, min_metrics, max_metrics, pooled_metrics;
     double forward_ms_per_image = 0.0;   // HIP events around the whole loop / samples
     int64_t num_parameters = 0;
@@ -258,7 +302,7 @@ public:
         pred_ = DeviceTensor::empty({B, 1, H, W}, d);
         cam_ = DeviceTensor::empty({B, 4}, d);
         rays_ = DeviceTensor();
-        MetricsTable table(ns, B, H, W, config_.min_depth, config_.max_depth, config_.clamp_pred, d);
+        MetricsTable table(ns, B, H, W, config_.min_depth, config_.max_depth, config_.clamp_pred, d, config_.align);
         cad_loader* ring = L.ring(B, d, false);
         cad::check(cad_loader_start_epoch(ring, nullptr, ns), "evaluation");
         cad_event *t0 = nullptr, *t1 = nullptr;
@@ -282,6 +326,8 @@ public:
             cad::check(cad_event_record(t1, nullptr), "event");
             cad_eval_summary s;
             r.per_sample = table.metrics(&s);
+            r.align = config_.align;
+            r.alignment = table.alignment(&r.aligned);
             float ms = 0.f;
             cad::check(cad_event_elapsed_ms(t0, t1, &ms), "event");
             r.forward_ms_per_image = (double)ms / (double)std::max<int64_t>(1, table.count());
