@@ -22,4 +22,7 @@ def __getattr__(name):
     if name in ("BatchAssembler", "AugSampler", "SunRGBDDataset", "PrefetchLoader"):
         from . import batch
         return getattr(batch, name)
+    if name in ("Predictor", "save_png", "load_png", "encode_png", "decode_png", "save_ply", "colormap_lut", "POINT_DTYPE"):
+        from . import export
+        return getattr(export, name)
     raise AttributeError(name)

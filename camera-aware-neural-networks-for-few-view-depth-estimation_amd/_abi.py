@@ -76,6 +76,16 @@ class EvalSummary(C.Structure):
     _fields_ = [("count", I64)] + [(k, F * 12) for k in ("mean", "std", "median", "min", "max", "pooled")]
 
 
+COLORMAPS = {"gray": 0, "jet": 1, "hot": 2}   # CAD_CMAP_*; 3 = CAD_CMAP_CUSTOM (cad_exporter_set_lut)
+CMAP_CUSTOM = 3
+
+
+class RenderOpts(C.Structure):
+    """cad_render_opts (cad.h)."""
+    _fields_ = [("colormap", I), ("fixed_range", I), ("lo", F), ("hi", F), ("invalid", C.c_uint8 * 3),
+                ("row_stride", I64), ("col_offset", I64), ("image_stride", I64), ("units_per_metre", F)]
+
+
 # name: (restype, argtypes)
 SIGNATURES = {
     "cad_abi_version": (I, []),
@@ -252,6 +262,19 @@ SIGNATURES = {
     "cad_loader_destroy": (None, [P]),
     "cad_loader_start_epoch": (I, [P, I64P, I64]),
     "cad_loader_next": (I, [P, P, P, P, P]),
+    "cad_colormap_lut": (I, [C.c_char_p, P]),
+    "cad_exporter_create": (I, [I, I, I, I, C.POINTER(P)]),
+    "cad_exporter_destroy": (None, [P]),
+    "cad_exporter_set_lut": (I, [P, P]),
+    "cad_exporter_range": (I, [P, P, P, P, I, P, P]),
+    "cad_exporter_render": (I, [P, P, P, P, I, C.POINTER(RenderOpts), P, P, P]),
+    "cad_exporter_image": (I, [P, P, I, C.POINTER(RenderOpts), P, P]),
+    "cad_exporter_points": (I, [P, P, P, P, P, I, I, F, F, P, P, P]),
+    "cad_hflip": (I, [P, P, I64, I, I, P]),
+    "cad_flip_mean": (I, [P, P, P, I64, I, I, P]),
+    "cad_png_encode": (I, [P, I, I, I, I, P, I64, I64P]),
+    "cad_png_decode": (I, [P, I64, P, I64, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+    "cad_ply_write": (I, [C.c_char_p, P, I64]),
 }
 
 

@@ -673,6 +673,24 @@ cad_status cad_jpeg_decode(const uint8_t* data, int64_t size, uint8_t* out, int6
     });
 }
 
+cad_status cad_png_decode(const uint8_t* data, int64_t size, void* out, int64_t cap, int* height, int* width, int* channels,
+                          int* bits) {
+    return data_guard([&] {
+        if (!data || size < 0) throw DataError("bad arguments");
+        const Image im = decode_png(std::string(reinterpret_cast<const char*>(data), (size_t)size), "<memory>");
+        if (height) *height = im.h;
+        if (width) *width = im.w;
+        if (channels) *channels = im.c;
+        if (bits) *bits = im.bits;
+        if (out) {
+            const size_t bytes = im.px.size() * (im.bits == 16 ? 2 : 1);
+            if (cap < (int64_t)bytes) throw DataError("output buffer too small");
+            if (im.bits == 16) std::memcpy(out, im.px.data(), bytes);
+            else std::copy(im.px.begin(), im.px.end(), static_cast<uint8_t*>(out));
+        }
+    });
+}
+
 cad_status cad_dataset_synthetic(int64_t n, int height, int width, uint32_t seed, cad_dataset** out) {
     return data_guard([&] {
         if (!out || n < 0 || height < 1 || width < 1) throw DataError("bad arguments");

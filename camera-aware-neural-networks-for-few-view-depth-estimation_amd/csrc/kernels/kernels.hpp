@@ -482,4 +482,28 @@ void pcl_fwd(const Pcl& P, const float* u, const float* camn, int B, int H, int 
 void pcl_bwd(const Pcl& P, const float* u, const float* camn, const float* g, int64_t ldg, int gcoff, int B, int H,
              int W, float* du, double* scratch, hipStream_t st);
 
+// Inference export (export_kernels.hip).  All tensors fp32 NCHW as the public API holds them; everything
+// runs on `st`, allocates nothing and never synchronises.  sub / mask / table / rgb are nullable.
+//   export_range   (min, max) of v = sub ? |d - sub| : d over each image's valid pixels -> table[b] (and
+//                  out[b] when given); part holds 2 * B * export_range_blocks(HW, B) floats
+//   export_render  depth -> RGB8 HWC pane through `lut` (768 bytes, 4-byte aligned; lo / hi from
+//                  table[b] or fixed) and / or uint16 rintf(d * units); the pane's strides are in pixels
+//   export_image   (B,3,H,W) rgb -> RGB8 HWC pane
+//   export_points  records[b * cap + i] = 16-byte {X, Y, Z, rgba} of image b's valid stride-grid pixels in
+//                  row-major order, counts[b] of them; tilecnt / tileoff hold B * export_point_tiles ints
+//   export_flip    out[r][x] = a ? 0.5f * (a[r][x] + b[r][W-1-x]) : b[r][W-1-x]; rows * W < 2^31; out may be a
+constexpr int kPointTile = 1024;   // candidates per tile of the ordered compaction
+int export_range_blocks(int64_t HW, int B);
+void export_range(const float* depth, const float* sub, const uint8_t* mask, int B, int64_t HW, float* part, float* table,
+                  float* out, hipStream_t st);
+void export_render(const float* depth, const float* sub, const uint8_t* mask, int B, int H, int W, const float* table, float lo,
+                   float hi, const uint8_t* lut, const uint8_t invalid[3], uint8_t* rgb, int64_t row_stride, int64_t col_off,
+                   int64_t image_stride, uint16_t* u16, float units, hipStream_t st);
+void export_image(const float* rgb, int B, int H, int W, uint8_t* dst, int64_t row_stride, int64_t col_off, int64_t image_stride,
+                  hipStream_t st);
+int export_point_tiles(int H, int W, int stride);
+void export_points(const float* depth, const float* K, const float* rgb, const uint8_t* mask, int B, int H, int W, int stride,
+                   float min_depth, float max_depth, int* tilecnt, int* tileoff, void* records, int* counts, hipStream_t st);
+void export_flip(const float* a, const float* b, float* out, int64_t rows, int W, hipStream_t st);
+
 }  // namespace cad

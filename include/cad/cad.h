@@ -58,6 +58,10 @@
  *                                   batch torch::stack + .to(device) (enhanced.h:277-289), on device
  *   cad_aug_sampler_create/draw     augmentSample's random draws (sunrgbd_loader.cpp:352-443;
  *                                   AugmentationConfig sunrgbd_loader.h:30-42, rng_ seed :185)
+ *   cad_exporter_* / cad_colormap_lut / cad_png_encode / cad_png_decode / cad_ply_write / cad_hflip /
+ *   cad_flip_mean                   DepthVisualizer (src/visualization/depth_viz.h:23-148,
+ *                                   depth_visualizer.h) on the device, 16-bit depth PNGs, point clouds
+ *                                   and flip test-time augmentation ("inference export" below)
  *   cad_op_*                        single operators of the step (conv, convT, BN, pool, ...), the
  *                                   ATen calls the reference dispatches
  *
@@ -702,6 +706,89 @@ cad_status cad_op_pcl(const float* u, const float* camn, const float* g, const f
 /* test hook: buffer of the last step ("cat<l>", "dcat<l>", "x<l>", "u<l>", "z<l>"; NHWC rows) -> host;
  * returns the element count (host NULL: count only) or -1 */
 int64_t cad_geonet_debug_buffer(cad_geonet* h, const char* name, float* host, int64_t numel);
+
+/* ---- inference export: depth renders, 16-bit depth, point clouds, PNG / PLY files.
+ *   cad_exporter_range / _render / _image   DepthVisualizer::normalizeDepth, applyColormap and the panes of
+ *                                   createComparisonViz, src/visualization/depth_viz.h:23-148 (and
+ *                                   depth_visualizer.h), on the device instead of through cv::Mat
+ *   cad_colormap_lut                cv::applyColorMap's tables (depth_viz.h:126-132), restated in integers
+ *   cad_png_encode / cad_png_decode cv::imwrite / cv::imread of depth_viz.h:81, sunrgbd_loader.cpp:221-259
+ *   cad_exporter_points, cad_ply_write, cad_hflip, cad_flip_mean
+ *                                   new: no reference counterpart (the mirrored intrinsics of flip
+ *                                   augmentation are applyHorizontalFlip's, sunrgbd_loader.cpp:416-430)
+ * The device calls run on the caller's stream, allocate nothing, never synchronise and never copy to the
+ * host; no floating-point atomics: an image's output is the same bits on every run, in whichever batch it
+ * arrives, from 16-byte aligned or unaligned tensors. */
+
+/* built-in colour tables, 256 x 3 bytes (r, g, b of index i), `/` floor division, clamped to [0, 255]:
+ *   gray (i, i, i);   jet (383 - |4i - 765|, 383 - |4i - 510|, 383 - |4i - 255|);
+ *   hot  (8i / 3, 8 max(i - 96, 0) / 3, max(0, 4 (i - 191) - 1)) */
+#define CAD_CMAP_GRAY 0
+#define CAD_CMAP_JET 1
+#define CAD_CMAP_HOT 2
+#define CAD_CMAP_CUSTOM 3 /* the table of cad_exporter_set_lut */
+/* host only (no device): name "gray" | "jet" | "hot" -> out768; another name: CAD_ERR_INVALID */
+cad_status cad_colormap_lut(const char* name, uint8_t* out768);
+
+typedef struct cad_exporter cad_exporter;
+/* owns every workspace (range table and partials, tile counts and scan space, the colour tables) for up to
+ * max_batch images of H x W.  Arguments are checked before any device call. */
+cad_status cad_exporter_create(int max_batch, int H, int W, int device, cad_exporter** out);
+void cad_exporter_destroy(cad_exporter* e);
+/* a caller's 768-byte table into the CAD_CMAP_CUSTOM slot (one synchronous upload) */
+cad_status cad_exporter_set_lut(cad_exporter* e, const uint8_t* lut768);
+/* per image (min, max) of v = sub ? |depth - sub| : depth over its valid pixels — isfinite(v), depth > 0
+ * (and sub > 0), mask != 0 — into the exporter's range table and, when out != NULL, into out (device, B x 2
+ * floats); (0, 0) without a valid pixel.  depth, sub: (B,1,H,W) device fp32; mask: B*H*W device bytes;
+ * sub and mask nullable. */
+cad_status cad_exporter_range(cad_exporter* e, const float* depth, const float* sub, const uint8_t* mask, int B, float* out,
+                              void* stream);
+typedef struct {
+    int colormap;          /* CAD_CMAP_* */
+    int fixed_range;       /* 0: each image's (lo, hi) from the range table (the last cad_exporter_range); 1: lo, hi */
+    float lo, hi;
+    uint8_t invalid[3];    /* colour of invalid pixels */
+    int64_t row_stride;    /* destination pixels per row; 0: W */
+    int64_t col_offset;    /* the pane's first column inside a destination row */
+    int64_t image_stride;  /* destination pixels between images; 0: H * row_stride */
+    float units_per_metre; /* of the 16-bit output: 1000 = SUN RGB-D's depth PNGs */
+} cad_render_opts;
+/* one pass over depth, two nullable outputs.  rgb_out: RGB8 HWC, pixel = LUT[idx] with t = (v - lo) / (hi - lo)
+ * (fp32 subtract, subtract, IEEE divide) clamped to [0, 1], idx = rintf(t * 255) (half to even); hi - lo < 1e-6:
+ * idx 0; invalid pixels (cad_exporter_range's rule): opts->invalid.  u16_out: (B,H,W) uint16,
+ * rintf(depth * units_per_metre) as one fp32 multiply, clamped to [0, 65535]; non-finite or depth <= 0: 0
+ * (sub and mask do not apply). */
+cad_status cad_exporter_render(cad_exporter* e, const float* depth, const float* sub, const uint8_t* mask, int B,
+                               const cad_render_opts* opts, uint8_t* rgb_out, uint16_t* u16_out, void* stream);
+/* rgb (B,3,H,W) fp32 -> RGB8 HWC pane, rintf(clamp(c, 0, 1) * 255); opts' strides and offset as above */
+cad_status cad_exporter_image(cad_exporter* e, const float* rgb, int B, const cad_render_opts* opts, uint8_t* rgb_out,
+                              void* stream);
+/* point cloud: pixel (y, x) of image b is emitted iff y % stride == 0, x % stride == 0, isfinite(Z),
+ * min_depth < Z < max_depth (strict) and mask != 0; its 16-byte record {float X, Y, Z; uint8 r, g, b, a} has
+ * X = (x - cx) / fx * Z, Y = (y - cy) / fy * Z (fp32 subtract, divide, multiply), Z the depth's bits,
+ * r g b = rintf(clamp(c, 0, 1) * 255) from rgb (B,3,H,W) or 255 without it, a = 255.  Records are in
+ * row-major pixel order; image b's start at records + b * cap * 16, cap = ceil(H/stride) * ceil(W/stride)
+ * (16-byte aligned, B * cap records); counts: device int32[B].  Bytes past an image's count stay untouched.
+ * K: (B,3,3) device.  rgb and mask nullable. */
+cad_status cad_exporter_points(cad_exporter* e, const float* depth, const float* K, const float* rgb, const uint8_t* mask,
+                               int B, int stride, float min_depth, float max_depth, void* records, int32_t* counts,
+                               void* stream);
+/* flip test-time augmentation: out[p][y][x] = in[p][y][W-1-x] (out must not overlap in), and
+ * out[p][y][x] = 0.5f * (a[p][y][x] + b[p][y][W-1-x]) (out may be a); planes * H * W < 2^31 */
+cad_status cad_hflip(const float* in, float* out, int64_t planes, int H, int W, void* stream);
+cad_status cad_flip_mean(const float* a, const float* b, float* out, int64_t planes, int H, int W, void* stream);
+
+/* host only.  PNG: non-interlaced, channels 1 (gray) or 3 (RGB), bits 8 (uint8 samples) or 16 (host-order
+ * uint16 samples, stored big-endian), h x w x channels samples in row-major order.  out == NULL: *size = an
+ * upper bound of the file size; else the file is written into out (cap bytes) and *size = its length. */
+cad_status cad_png_encode(const void* pixels, int h, int w, int channels, int bits, uint8_t* out, int64_t cap, int64_t* size);
+/* the loader's PNG decoder on a file held in memory: 8- or 16-bit gray, gray + alpha, RGB, RGBA, 8-bit
+ * palette (as RGB); samples as above into out (cap bytes; out == NULL: dimensions only) */
+cad_status cad_png_decode(const uint8_t* data, int64_t size, void* out, int64_t cap, int* height, int* width, int* channels,
+                          int* bits);
+/* binary_little_endian 1.0 PLY: properties float x y z, uchar red green blue alpha; the body is the n x 16
+ * record bytes of cad_exporter_points (host copy) */
+cad_status cad_ply_write(const char* path, const void* records, int64_t n);
 
 #ifdef __cplusplus
 }
