@@ -25,4 +25,7 @@ def __getattr__(name):
     if name in ("Predictor", "save_png", "load_png", "encode_png", "decode_png", "save_ply", "colormap_lut", "POINT_DTYPE"):
         from . import export
         return getattr(export, name)
+    if name in ("read_events", "SummaryWriter", "EventFileError", "crc32c", "masked_crc32c", "default_bins", "trim_histogram"):
+        from . import tbevents
+        return getattr(tbevents, name)
     raise AttributeError(name)

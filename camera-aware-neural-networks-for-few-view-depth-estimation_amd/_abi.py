@@ -20,6 +20,7 @@ I = C.c_int
 I64 = C.c_int64
 FP = C.POINTER(C.c_float)
 I64P = C.POINTER(C.c_int64)
+DP = C.POINTER(C.c_double)
 
 
 class UnetDesc(C.Structure):
@@ -85,6 +86,15 @@ class RenderOpts(C.Structure):
     _fields_ = [("colormap", I), ("fixed_range", I), ("lo", F), ("hi", F), ("invalid", C.c_uint8 * 3),
                 ("row_stride", I64), ("col_offset", I64), ("image_stride", I64), ("units_per_metre", F)]
 
+
+class HistSegment(C.Structure):
+    """cad_hist_segment (cad.h): element i of base[offset : offset + count] counts iff r = i % period < keep
+    (and, with an inner rule, r % inner_period < inner_keep)."""
+    _fields_ = [("offset", I64), ("count", I64), ("period", I64), ("keep", I64), ("inner_period", I64), ("inner_keep", I64)]
+
+
+HIST_BINS = 1548    # CAD_HIST_BINS
+HIST_STATS = ("num", "min", "max", "sum", "sum_squares", "nonfinite")   # a row of cad_hist_read
 
 # name: (restype, argtypes)
 SIGNATURES = {
@@ -275,6 +285,29 @@ SIGNATURES = {
     "cad_png_encode": (I, [P, I, I, I, I, P, I64, I64P]),
     "cad_png_decode": (I, [P, I64, P, I64, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
     "cad_ply_write": (I, [C.c_char_p, P, I64]),
+    "cad_crc32c": (C.c_uint32, [P, I64]),
+    "cad_crc32c_masked": (C.c_uint32, [P, I64]),
+    "cad_tb_open": (I, [C.c_char_p, C.POINTER(P)]),
+    "cad_tb_close": (None, [P]),
+    "cad_tb_flush": (I, [P]),
+    "cad_tb_path": (C.c_char_p, [P]),
+    "cad_tb_hparams_path": (C.c_char_p, [P]),
+    "cad_tb_scalar": (I, [P, C.c_char_p, F, I64]),
+    "cad_tb_histogram": (I, [P, C.c_char_p, I64, DP, DP, DP, I]),
+    "cad_tb_image": (I, [P, C.c_char_p, I64, I, I, I, P, I64]),
+    "cad_tb_text": (I, [P, C.c_char_p, I64, C.c_char_p]),
+    "cad_tb_custom_scalars": (I, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), I]),
+    "cad_tb_hparams": (I, [P, C.POINTER(C.c_char_p), DP, I, C.POINTER(C.c_char_p), FP, I, C.c_char_p]),
+    "cad_tb_default_bins": (I, [DP, I]),
+    "cad_tb_trim_histogram": (I, [C.POINTER(C.c_uint32), I, DP, DP, DP, C.POINTER(I)]),
+    "cad_hist_create": (I, [C.POINTER(HistSegment), I, I, C.POINTER(P)]),
+    "cad_hist_destroy": (None, [P]),
+    "cad_hist_num_segments": (I, [P]),
+    "cad_hist_run": (I, [P, P, P]),
+    "cad_hist_read": (I, [P, DP, C.POINTER(C.c_uint32)]),
+    "cad_unet_histograms": (I, [P, I, P, C.POINTER(P)]),
+    "cad_resunet_histograms": (I, [P, I, P, C.POINTER(P)]),
+    "cad_geonet_histograms": (I, [P, I, P, C.POINTER(P)]),
 }
 
 

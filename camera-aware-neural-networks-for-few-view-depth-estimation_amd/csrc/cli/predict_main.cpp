@@ -370,15 +370,7 @@ int run(Args a) {
         if (a.depth_png) ex.depth16(pred.data, n, u16_d.as<uint16_t>());
         if (a.color_png) ex.color(pred.data, nullptr, n, cmap, cad::Exporter::Pane{color_d.as<uint8_t>(), 0, 0}, a.range.empty() ? nullptr : a.range.data());
         if (a.ply) ex.points(pred.data, K.data, rgb.data, n, a.ply_stride, 0.1f, c.max_depth, rec_d.p, cnt_d.as<int32_t>());
-        if (a.panel) {   // createComparisonViz: rgb | gt | pred | error
-            uint8_t* p = panel_d.as<uint8_t>();
-            ex.image(rgb.data, n, cad::Exporter::Pane{p, 4 * W, 0});
-            ex.range(gt.data, nullptr, n);
-            ex.color(gt.data, nullptr, n, cmap, cad::Exporter::Pane{p, 4 * W, W});
-            ex.color(pred.data, nullptr, n, cmap, cad::Exporter::Pane{p, 4 * W, 2 * W});
-            ex.range(pred.data, gt.data, n);
-            ex.color(pred.data, gt.data, n, CAD_CMAP_HOT, cad::Exporter::Pane{p, 4 * W, 3 * W});
-        }
+        if (a.panel) ex.comparison_panel(rgb.data, gt.data, pred.data, n, cmap, panel_d.as<uint8_t>());   // createComparisonViz
         float ms = 0.f;
         cad::check(cad_event_elapsed_ms(t0, t1, &ms), "event");
         // the copies below are synchronous on the default stream, after everything above

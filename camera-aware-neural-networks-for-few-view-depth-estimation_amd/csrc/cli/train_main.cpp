@@ -13,7 +13,8 @@
 // any exception prints "Error: <what>" and exits 1 (:503-506).
 // Deliberate differences: the model lives on the GPU (the reference never moves it,
 // SURVEY §0 fact 2); --resume really resumes (params + BN buffers + Adam state; the reference parses
-// and ignores it); TensorBoard events are written as a CSV of scalars (no Python tensorboard here);
+// and ignores it); TensorBoard event files are written natively (trainer.hpp: no Python subprocess) under
+// logging.tensorboard.tensorboard_dir/<experiment>, next to the CSV of scalars in the log directory;
 // model.architecture selects the FiLM models and the geometry-aware networks (model.variant,
 // use_pcl, use_attention; single process) — the reference always builds BaselineUNet;
 // data.dataset_name "synthetic" trains on generated samples, anything else on the manifest's PNG / PNM /
@@ -64,7 +65,9 @@ void usage() {
                  "                        .pt: torch::save model archive, weights only)\n"
                  "  -g, --gpu arg         GPU ID (default: 0)\n"
                  "  -d, --debug           Enable debug mode\n"
-                 "      --tensorboard arg Enable TensorBoard-style scalar logging (default: true)\n"
+                 "      --tensorboard arg Write TensorBoard event files (scalars, histograms, prediction panels) under\n"
+                 "                        logging.tensorboard.tensorboard_dir/<experiment> and the scalars CSV in\n"
+                 "                        the log directory (default: true; false writes neither)\n"
                  "      --dry-run         Print the run plan (per data-parallel rank) and exit; no GPU use\n"
                  "  -h, --help            Print help\n";
 }
@@ -103,6 +106,9 @@ struct Config {   // the TrainingConfig fields the step uses (trainer.h:24-92)
     float si = 1.0f, grad = 0.1f, smooth = 0.001f, reproj = 0.01f, max_depth = 10.0f;
     int init_features = 64, height = 240, width = 320, seed = 42;
     std::string checkpoint_dir = "./checkpoints", log_dir = "./logs", experiment_name = "baseline_unet";
+    // logging.tensorboard / visualization (train_main.cpp:421-430)
+    std::string tensorboard_dir = "./runs";
+    int viz_interval = 1, num_viz_samples = 4, histogram_interval = 5;
     std::string dataset = "sunrgbd", data_dir = "./data/sunrgbd";
     std::string manifest_path = "./data/sunrgbd_manifest.json";
     std::vector<std::string> sensor_types;   // data.sensor_types (empty: all four)
@@ -147,7 +153,15 @@ Config load_config(const yaml_lite::Node& y, const std::string& experiment) {   
         c.checkpoint_dir = k["checkpoint_dir"].as<std::string>("./checkpoints");
         c.save_interval = k["save_interval"].as<int>(5);
     }
-    if (auto& l = y["logging"]) c.log_dir = l["log_dir"].as<std::string>("./logs");
+    if (auto& l = y["logging"]) {
+        c.log_dir = l["log_dir"].as<std::string>("./logs");
+        if (auto& t = l["tensorboard"]) {
+            c.tensorboard_dir = t["tensorboard_dir"].as<std::string>("./runs");
+            c.viz_interval = t["log_image_interval"].as<int>(1);
+            c.histogram_interval = t["log_histogram_interval"].as<int>(5);
+        }
+    }
+    if (auto& v = y["visualization"]) c.num_viz_samples = v["num_viz_samples"].as<int>(4);
     if (auto& e = y["experiment"]) {
         c.experiment_name = e["name"].as<std::string>(experiment);
         c.seed = e["seed"].as<int>(42);
@@ -348,7 +362,7 @@ Shard shard_of(int bi, int n_train, int B, const Rank& r) {
     return {first, (int)std::min<int64_t>(B, n_train - first)};
 }
 
-int dry_run(const Config& c, const Rank& r) {
+int dry_run(const Config& c, const Rank& r, bool tensorboard) {
     const auto id = exchange_id(r, true);
     uint64_t h = 1469598103934665603ull;   // FNV-1a of the rendezvous bytes: equal on every rank
     for (uint8_t b : id) h = (h ^ b) * 1099511628211ull;
@@ -366,7 +380,9 @@ int dry_run(const Config& c, const Rank& r) {
     const Shard s0 = shard_of(0, c.n_train, c.batch_size, r);
     o << s0.first << ", " << s0.first + s0.n << "], \"n_flat\": " << n_flat << ", \"buckets\": [";
     for (int i = 0; i < nb; ++i) o << (i ? ", " : "") << "[" << boff[i] << ", " << bcnt[i] << ", " << blast[i] << "]";
-    o << "]}";
+    o << "]";
+    // the lead rank's TensorBoard event directory ("" when it writes none)
+    o << ", \"event_dir\": \"" << (tensorboard && r.rank == 0 ? c.tensorboard_dir + "/" + c.experiment_name : std::string()) << "\"}";
     std::cout << o.str() << std::endl;
     return 0;
 }
@@ -399,7 +415,7 @@ int run(const Args& args) {
         c.n_val = std::min(500, c.n_train);
         if (c.n_train == 0) throw std::runtime_error("no usable samples in " + c.manifest_path);
     }
-    if (args.dry_run) return dry_run(c, R);
+    if (args.dry_run) return dry_run(c, R, args.tensorboard);
     const bool lead = R.rank == 0;   // logs, validation and checkpoints (rank 0's replica)
     if (lead) std::cout << "Loading configuration from: " << args.config << "\n";
     if (args.debug && lead) std::cout << "Debug mode enabled - using reduced dataset\n";
@@ -462,6 +478,11 @@ int run(const Args& args) {
         gc.log_dir = c.log_dir;
         gc.experiment_name = c.experiment_name;
         gc.device = R.device;
+        gc.tensorboard = args.tensorboard;
+        gc.tensorboard_dir = c.tensorboard_dir;
+        gc.viz_interval = c.viz_interval;
+        gc.num_viz_samples = c.num_viz_samples;
+        gc.histogram_interval = c.histogram_interval;
         GeometryTrainer gt(geo, gloss, gc);
         gt.train(train_loader, val_loader);
         std::cout << "Training complete.\n";
@@ -499,6 +520,10 @@ int run(const Args& args) {
     tc.experiment_name = c.experiment_name;
     tc.device = R.device;
     tc.tensorboard = args.tensorboard;
+    tc.tensorboard_dir = c.tensorboard_dir;
+    tc.viz_interval = c.viz_interval;
+    tc.num_viz_samples = c.num_viz_samples;
+    tc.histogram_interval = c.histogram_interval;
     TensorBoardTrainerEnhanced trainer(model, model, loss_fn, tc, comm);
     if (!args.resume.empty()) {
         trainer.loadCheckpoint(args.resume);

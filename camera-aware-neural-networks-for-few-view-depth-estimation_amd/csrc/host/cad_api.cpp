@@ -226,6 +226,7 @@ struct cad_unet {
     int64_t part_cap = 0;
     // stage grad ranges
     std::vector<std::pair<int64_t, int64_t>> stage_range;
+    cad_hist* hist = nullptr;   // cad_unet_histograms: created on first use, one segment per parameter
 
     int Hl(int l) const { return H >> l; }
     int Wl(int l) const { return W >> l; }
@@ -1136,6 +1137,7 @@ void cad_unet_destroy(cad_unet* h) {
     for (hipEvent_t e : {h->ev_fork, h->evA, h->evB, h->ev_tail})
         if (e) (void)hipEventDestroy(e);
     if (h->side) (void)hipStreamDestroy(h->side);
+    cad_hist_destroy(h->hist);
     (void)hipFree(h->arena_base);
     delete h;
 }
@@ -1213,6 +1215,28 @@ cad_status cad_unet_get_grad(const cad_unet* h, int idx, float* host, int64_t nu
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipDeviceSynchronize());
         get_slab_tensor(h, h->flat_g, idx, host, numel);
+    });
+}
+
+cad_status cad_unet_histograms(cad_unet* h, int which, void* stream, cad_hist** hist) {
+    return guard([&] {
+        require(h && (which == 0 || which == 1), "histograms: which must be 0 (parameters) or 1 (gradients)");
+        HIPCHK(hipSetDevice(h->device));
+        if (!h->hist) {
+            // the packed layout keeps a tensor's values as a multiset; only padding must stay out: the zero
+            // input channels of enc1.conv1 ([co][tap][cin_int], cin_ref of every cin_int real) and the gaps
+            // between the 256-byte aligned tensors (not covered by any segment)
+            std::vector<cad_hist_segment> segs;
+            for (const PInfo& p : h->params) {
+                const bool padded = p.kind == P_CONV3 && p.cin_int != p.cin_ref;
+                segs.push_back(cad_hist_segment{p.off, p.n_int, padded ? p.cin_int : 1, padded ? p.cin_ref : 1, 0, 0});
+            }
+            const cad_status sc = cad_hist_create(segs.data(), (int)segs.size(), h->device, &h->hist);
+            if (sc != CAD_OK) throw CadError(sc, g_err);
+        }
+        const cad_status st = cad_hist_run(h->hist, which == 0 ? h->flat_p : h->flat_g, stream);
+        if (st != CAD_OK) throw CadError(st, g_err);
+        if (hist) *hist = h->hist;
     });
 }
 

@@ -149,6 +149,7 @@ struct cad_geonet {
     std::vector<GBuf> bufs;
     int64_t n_flat = 0;
     float *flat_p = nullptr, *flat_g = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+    cad_hist* hist = nullptr;   // cad_geonet_histograms: created on first use, one segment per parameter
     int64_t adam_t = 0;
     float* norm_coef = nullptr;
     void* base = nullptr;
@@ -730,6 +731,7 @@ void cad_geonet_destroy(cad_geonet* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
+    cad_hist_destroy(h->hist);
     (void)hipFree(h->base);
     delete h;
 }
@@ -796,6 +798,23 @@ cad_status cad_geonet_get_grad(const cad_geonet* h, int idx, float* host, int64_
         GCHK(hipSetDevice(h->device));
         GCHK(hipDeviceSynchronize());
         geo_get(h, h->flat_g, idx, host, numel);
+    });
+}
+
+cad_status cad_geonet_histograms(cad_geonet* h, int which, void* stream, cad_hist** hist) {
+    return gguard([&] {
+        need(h && (which == 0 || which == 1), "histograms: which must be 0 (parameters) or 1 (gradients)");
+        GCHK(hipSetDevice(h->device));
+        if (!h->hist) {   // as cad_unet_histograms: only the zero-padded input channels of a 3x3 convolution are skipped
+            std::vector<cad_hist_segment> segs;
+            for (const GParam& p : h->params) {
+                const bool padded = p.kind == G_CONV3 && p.cin_int != p.cin_ref;
+                segs.push_back(cad_hist_segment{p.off, p.n_int, padded ? p.cin_int : 1, padded ? p.cin_ref : 1, 0, 0});
+            }
+            need(cad_hist_create(segs.data(), (int)segs.size(), h->device, &h->hist) == CAD_OK, cad_last_error());
+        }
+        need(cad_hist_run(h->hist, which == 0 ? h->flat_p : h->flat_g, stream) == CAD_OK, cad_last_error());
+        if (hist) *hist = h->hist;
     });
 }
 

@@ -175,6 +175,7 @@ struct cad_resunet {
     std::vector<RBuf> bufs;
     int64_t n_flat = 0;
     float *flat_p = nullptr, *flat_g = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+    cad_hist* hist = nullptr;   // cad_resunet_histograms: created on first use, one segment per parameter
     int64_t adam_t = 0;
     float* norm_coef = nullptr;
     void* base = nullptr;
@@ -1043,6 +1044,7 @@ void cad_resunet_destroy(cad_resunet* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
+    cad_hist_destroy(h->hist);
     (void)hipFree(h->base);
     delete h;
 }
@@ -1140,6 +1142,27 @@ int cad_resunet_fp8_units(const cad_resunet* h) {
     for (const Bott& b : h->blocks) { cnt(b.u1); cnt(b.u2); cnt(b.u3); cnt(b.ud); }
     for (const Dec& d : h->dec) { cnt(d.u1); cnt(d.u2); }
     return n;
+}
+
+cad_status cad_resunet_histograms(cad_resunet* h, int which, void* stream, cad_hist** hist) {
+    return rguard([&] {
+        need(h && (which == 0 || which == 1), "histograms: which must be 0 (parameters) or 1 (gradients)");
+        RCHK(hipSetDevice(h->device));
+        if (!h->hist) {
+            // a convolution is [co][Kp] with Kp = k*k*cin_int rounded up to 8 floats and tap t's channels at
+            // t*cin_int: the row's tail and the channels past cin_ref (the stem: 3 of 4) are padding
+            std::vector<cad_hist_segment> segs;
+            for (const RParam& p : h->params) {
+                if (p.kind != R_CONV) { segs.push_back(cad_hist_segment{p.off, p.n_int, 1, 1, 0, 0}); continue; }
+                const int64_t taps = (int64_t)p.k * p.k * p.cin_int;
+                if (p.cin_int == p.cin_ref) segs.push_back(cad_hist_segment{p.off, p.n_int, p.Kp, taps, 0, 0});
+                else segs.push_back(cad_hist_segment{p.off, p.n_int, p.Kp, taps, p.cin_int, p.cin_ref});
+            }
+            need(cad_hist_create(segs.data(), (int)segs.size(), h->device, &h->hist) == CAD_OK, cad_last_error());
+        }
+        need(cad_hist_run(h->hist, which == 0 ? h->flat_p : h->flat_g, stream) == CAD_OK, cad_last_error());
+        if (hist) *hist = h->hist;
+    });
 }
 
 cad_status cad_resunet_flat(cad_resunet* h, float** params, float** grads, int64_t* n) {

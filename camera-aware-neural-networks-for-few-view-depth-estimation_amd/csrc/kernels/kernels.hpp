@@ -304,6 +304,25 @@ void head_bwd_y(const float* y, int C, const float* scale, const float* shift, c
 int metrics_blocks(int64_t HW);
 void depth_metrics_partials(const float* pred, const float* gt, int B, int64_t HW, double* part, int nb,
                             hipStream_t st);
+// Device histograms of a flat fp32 slab (hist_kernels.hip; handle: host/hist.cpp, cad_hist_* in cad.h).
+// segs / chunks / ukey are the handle's device tables: ukey[k] = order key of the smallest fp32 >= edge k
+// (kHistBins + 1 of them), key_hi = order key of the largest fp32 <= the last edge.  stats [nseg][kHistStats]
+// doubles {num, min, max, sum, sum_squares, nonfinite} and bins [nseg][kHistBins] are one allocation (stats
+// first); part: [nchunks][kHistStats] doubles; span: floats of `base` the segments cover (aliasing guard).
+constexpr int kHistBins = 1548;
+constexpr int kHistStats = 6;
+constexpr int kHistChunk = 16384;   // elements per chunk: 64 per thread of a 256-thread block
+struct HistSegment {
+    int64_t offset, count, period, keep;
+    int64_t inner_period, inner_keep;   // 0: no inner rule
+    int first_chunk, nchunks;
+};
+struct HistChunk {
+    int64_t start;   // first element, relative to the segment
+    int seg, len;
+};
+void hist_run(const float* base, const HistSegment* segs, int nseg, const HistChunk* chunks, int nchunks, const unsigned* ukey,
+              unsigned key_hi, double* stats, unsigned* bins, double* part, int64_t span, hipStream_t st);
 // Offline evaluation (eval_kernels.hip): the twelve sums of DepthMetrics::compute per sample, {n, |d|/g,
 // d^2/g, d^2, dln^2, |d|, |dlog10|, a1, a2, a3, p, g}.  part: [B][nb][12] doubles (nb = eval_blocks(HW));
 // rows base .. base + B - 1 of table ([rows][12] doubles, device) receive the sums.  mask nullable.

@@ -40,6 +40,23 @@ def _ptr(t: torch.Tensor):
 MODEL_BASELINE, MODEL_INTRINSICS_FILM, MODEL_RAY_FILM = 0, 1, 2   # CAD_MODEL_* of cad.h
 
 
+def _histograms(model, fn, which):
+    """TensorBoard histograms of every parameter ("params") or gradient ("grads") tensor from one device pass
+    over the model's flat slab (cad_*_histograms): name -> (stats, counts) in named_parameters() order, stats a
+    dict of _abi.HIST_STATS, counts the uint32 array of the _abi.HIST_BINS default buckets."""
+    if which not in ("params", "grads"):
+        raise ValueError(f"which must be 'params' or 'grads', not {which!r}")
+    hh = C.c_void_p()
+    check(fn(model.h, 0 if which == "params" else 1, _stream(model.device), C.byref(hh)), "histograms")
+    n = len(model._param_info)
+    stats = np.empty((n, len(_abi.HIST_STATS)), np.float64)
+    counts = np.empty((n, _abi.HIST_BINS), np.uint32)
+    check(model.lib.cad_hist_read(hh, stats.ctypes.data_as(_abi.DP), counts.ctypes.data_as(C.POINTER(C.c_uint32))),
+          "cad_hist_read")
+    return OrderedDict((name, (dict(zip(_abi.HIST_STATS, stats[i].tolist())), counts[i]))
+                       for i, (name, _) in enumerate(model._param_info))
+
+
 class BaselineUNet:
     """BaselineUNetImpl(in_channels, init_features, max_depth) on MI355X.
 
@@ -191,6 +208,10 @@ class BaselineUNet:
 
     def num_batches_tracked(self) -> int:
         return int(self.lib.cad_unet_num_batches_tracked(self.h))
+
+    def histograms(self, which="params") -> "OrderedDict[str, tuple]":
+        """name -> (stats, counts) of every parameter ("params") or gradient ("grads") tensor: _histograms."""
+        return _histograms(self, self.lib.cad_unet_histograms, which)
 
     def last_grad_norm(self) -> float:
         v = C.c_float()
@@ -838,6 +859,10 @@ class ResNetUNet:
 
     def count_parameters(self) -> int:
         return int(self._f("count_parameters")(self.h))
+
+    def histograms(self, which="params") -> "OrderedDict[str, tuple]":
+        """name -> (stats, counts) of every parameter ("params") or gradient ("grads") tensor: _histograms."""
+        return _histograms(self, self._f("histograms"), which)
 
     def _get(self, kind, idx, shape):
         out = np.empty(int(np.prod(shape)) if shape else 1, np.float32)

@@ -790,6 +790,92 @@ cad_status cad_png_decode(const uint8_t* data, int64_t size, void* out, int64_t 
  * record bytes of cad_exporter_points (host copy) */
 cad_status cad_ply_write(const char* path, const void* records, int64_t n);
 
+/* ---- TensorBoard event files (host only, csrc/host/tfevents.cpp): what the reference sends through
+ * tensorboard_logger_v2.h -> scripts/tensorboard_writer.py, written natively.
+ * File: <logdir>/events.out.tfevents.<unix seconds>.<hostname>.<pid>.<k>, k a per-process counter (0 for the
+ * first writer), the directory created; every writer opens a new file and never appends to an old one.
+ * Record: uint64 LE length, uint32 masked CRC-32C of those 8 bytes, payload, uint32 masked CRC-32C of the
+ * payload; mask(c) = ((c >> 15 | c << 17) + 0xa282ead8) mod 2^32.  Payloads are hand-encoded protobuf wire
+ * format (Event / Summary / HistogramProto / TensorProto and the text, custom_scalars and hparams plugin
+ * messages).  The file-version, scalar, text, custom_scalars and hparams records are byte for byte what
+ * TensorBoard's own writer produces for the same content (pinned by the files under tests/golden/tfevents);
+ * histogram and image records are valid for every parser but not pinned to its bytes (a proto3 serializer
+ * leaves out a statistic that is 0.0, cad_tb_histogram always writes all five).  The first record is
+ * Event{wall_time, file_version "brain.Event:2", source_metadata}; a step of 0 is left out as proto3 does. */
+uint32_t cad_crc32c(const void* data, int64_t size);          /* Castagnoli; "123456789" -> 0xE3069283 */
+uint32_t cad_crc32c_masked(const void* data, int64_t size);
+typedef struct cad_tb_writer cad_tb_writer;
+cad_status cad_tb_open(const char* logdir, cad_tb_writer** out);
+void cad_tb_close(cad_tb_writer* w);                          /* flushes; also closes the hparams sub-run */
+cad_status cad_tb_flush(cad_tb_writer* w);
+const char* cad_tb_path(const cad_tb_writer* w);              /* the event file */
+cad_status cad_tb_scalar(cad_tb_writer* w, const char* tag, float value, int64_t step);
+/* stats: {min, max, num, sum, sum_squares}; limits: n right bucket edges; buckets: n counts (doubles) */
+cad_status cad_tb_histogram(cad_tb_writer* w, const char* tag, int64_t step, const double stats[5], const double* limits,
+                            const double* buckets, int n);
+/* png: an encoded PNG (cad_png_encode); colorspace 3 = RGB, 1 = gray */
+cad_status cad_tb_image(cad_tb_writer* w, const char* tag, int64_t step, int height, int width, int colorspace,
+                        const void* png, int64_t bytes);
+/* text plugin record under tag + "/text_summary" */
+cad_status cad_tb_text(cad_tb_writer* w, const char* tag, int64_t step, const char* text);
+/* custom-scalars layout: n rows (category, chart, tag) in display order; consecutive rows sharing a category
+ * (and chart) are grouped; every chart is a multiline chart */
+cad_status cad_tb_custom_scalars(cad_tb_writer* w, const char* const* categories, const char* const* charts,
+                                 const char* const* tags, int n);
+/* hyper-parameters (all float64, written sorted by name) into the sub-run <logdir>/<subdir> (NULL: the wall
+ * clock as seconds.microseconds) with its own event file: _hparams_/experiment, _hparams_/session_start_info,
+ * _hparams_/session_end_info, then the metric scalars at step 0 */
+cad_status cad_tb_hparams(cad_tb_writer* w, const char* const* names, const double* values, int n,
+                          const char* const* metric_tags, const float* metric_values, int nmetrics, const char* subdir);
+const char* cad_tb_hparams_path(const cad_tb_writer* w);      /* the sub-run's event file ("" before cad_tb_hparams) */
+
+/* TensorBoard's default histogram buckets as torch.utils.tensorboard builds them, in double: v = 1e-12;
+ * while v < 1e20: append v, v *= 1.1; edges = the negated list reversed, 0, the list.  Returns the number of
+ * edges (CAD_HIST_BINS + 1) and writes min(cap, that) of them (edges NULL: count only). */
+#define CAD_HIST_BINS 1548
+int cad_tb_default_bins(double* edges, int cap);
+/* make_histogram's trimming (torch/utils/tensorboard/summary.py): first through last non-empty bucket plus one
+ * empty bucket on the left; limits are the right edges.  counts: nbins; edges: nbins + 1; limits / buckets:
+ * room for nbins + 1.  No non-empty bucket: the single pair (0, 0). */
+cad_status cad_tb_trim_histogram(const uint32_t* counts, int nbins, const double* edges, double* limits, double* buckets,
+                                 int* n);
+
+/* ---- device histograms over a base pointer and a segment table (csrc/kernels/hist_kernels.hip).
+ * Element i of a segment (base[offset + i], i < count) is counted iff i % period < keep.  Buckets are
+ * cad_tb_default_bins' with numpy.histogram's rule on the values widened to double: half-open [a, b), the last
+ * bin closed, values outside [edges[0], edges[last]] in no bucket, -0.0 with 0.0 in [0, 1e-12); the bucket is
+ * found by exact integer comparison against "the smallest fp32 not below edge k".  Per segment
+ * {num, min, max, sum, sum_squares, nonfinite}: non-finite values count in nonfinite only; num is the number
+ * of counted finite values (in a bucket or not); sums are double (products formed in double), reduced in a
+ * fixed order without floating-point atomics: a row is the same bits on every run.  num == 0: min = max = 0. */
+typedef struct {
+    int64_t offset, count, period, keep;
+    /* optional second rule inside a period, for rows that are padded twice (a convolution row of `period` floats
+     * whose first `keep` hold taps of inner_period channels, inner_keep of them real): with r = i % period the
+     * element counts iff r < keep && r % inner_period < inner_keep.  0, 0: no inner rule. */
+    int64_t inner_period, inner_keep;
+} cad_hist_segment;
+#define CAD_HIST_STATS 6
+typedef struct cad_hist cad_hist;
+cad_status cad_hist_create(const cad_hist_segment* segments, int nseg, int device, cad_hist** out);
+void cad_hist_destroy(cad_hist* h);
+int cad_hist_num_segments(const cad_hist* h);
+/* asynchronous on stream, allocates nothing, never synchronises, clears its own bins */
+cad_status cad_hist_run(cad_hist* h, const float* base, void* stream);
+/* one synchronous copy of the last run: stats [nseg][CAD_HIST_STATS] doubles, counts [nseg][CAD_HIST_BINS]
+ * (either nullable) */
+cad_status cad_hist_read(cad_hist* h, double* stats, uint32_t* counts);
+/* the pass over a U-Net's parameter (which = 0) or gradient (1) slab: one segment per named_parameters()
+ * entry, in that order, counting exactly the values cad_unet_get_tensor / cad_unet_get_grad return (the
+ * zero-padded input channels of enc1.conv1 and the alignment gaps are skipped).  The handle is created on
+ * the first call and owned by the model; read it with cad_hist_read. */
+cad_status cad_unet_histograms(cad_unet* h, int which, void* stream, cad_hist** hist);
+/* the same for the ResNet-50-encoder U-Net and the geometry-aware networks: one slab, one segment per
+ * named_parameters() entry (a ResNet convolution row is padded to a multiple of 8 floats and the stem's
+ * three input channels to four: both skipped) */
+cad_status cad_resunet_histograms(cad_resunet* h, int which, void* stream, cad_hist** hist);
+cad_status cad_geonet_histograms(cad_geonet* h, int which, void* stream, cad_hist** hist);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,19 @@ public:
         const cad_render_opts o = opts(pane);
         check(cad_exporter_image(h_, rgb, B, &o, pane.rgb, stream), "cad_exporter_image");
     }
+    // createComparisonViz's strip rgb | gt | pred | |pred - gt| of n samples into `panel` (device, n x H x 4W RGB8):
+    // gt and pred in gt's range with `colormap`, the error pane in its own range with the hot table
+    // (build/predict's <stem>_panel.png and the trainers' predictions/sample_<i> panels)
+    void comparison_panel(const float* rgb, const float* gt, const float* pred, int n, int colormap, uint8_t* panel,
+                          void* stream = nullptr) {
+        const int64_t W = W_;
+        image(rgb, n, Pane{panel, 4 * W, 0}, stream);
+        range(gt, nullptr, n, nullptr, stream);
+        color(gt, nullptr, n, colormap, Pane{panel, 4 * W, W}, nullptr, stream);
+        color(pred, nullptr, n, colormap, Pane{panel, 4 * W, 2 * W}, nullptr, stream);
+        range(pred, gt, n, nullptr, stream);
+        color(pred, gt, n, CAD_CMAP_HOT, Pane{panel, 4 * W, 3 * W}, nullptr, stream);
+    }
     int64_t point_capacity(int stride) const { return (int64_t)((H_ + stride - 1) / stride) * ((W_ + stride - 1) / stride); }
     void points(const float* depth, const float* K, const float* rgb, int B, int stride, float min_depth, float max_depth,
                 void* records, int32_t* counts, void* stream = nullptr) {

@@ -9,8 +9,14 @@
 // clip_grad_norm_, Adam.step, enhanced.h:287-304) on the MI355X through libcad.  Batches come from the
 // loader's prefetch ring (cad_loader: decode threads, pinned double-buffered upload, device resize and
 // augmentation) instead of getBatch + torch::stack.  Deliberate differences:
-//   * TensorBoard event files are a CSV of scalars (<log_dir>/tensorboard_scalars.csv); images and
-//     histograms are not written (gradients/norm|max|min scalars are);
+//   * TensorBoard event files are written natively (cad_tb_* in cad.h, no Python subprocess) under
+//     <tensorboard_dir>/<experiment_name>: every scalar (also kept as <log_dir>/tensorboard_scalars.csv), the
+//     custom-scalars layout, the hparams sub-run and the model/architecture text at the start of train(),
+//     weights/* and gradients/* histograms every histogram_interval epochs, predictions/sample_<i> panels
+//     (rgb | gt | pred | error) every viz_interval epochs.  Histograms cover every element of a tensor from one
+//     device pass over the slab (the reference samples at most 10 000 strided values per tensor on the host),
+//     and gradients/norm|max|min come from that pass's statistics.  GeometryTrainer writes the same records
+//     (cad_geonet_histograms over its slab), and no CSV, as before;
 //   * with a distributed::Communicator the step is data-parallel (the reference is single-device):
 //     rank r trains its batch_size-slice of every global batch, gradients are SUM-all-reduced in
 //     buckets overlapped with the backward and clipped as the mean; rank 0 validates, logs and saves;
@@ -33,6 +39,7 @@
 #include <thread>
 
 #include "cad.hpp"
+#include "exporter.hpp"
 
 namespace camera_aware_depth {
 
@@ -127,6 +134,157 @@ private:
     AugmentationConfig aug_{};
     std::vector<std::pair<std::tuple<int, int, bool>, std::shared_ptr<cad_loader>>> rings_;
 };
+
+// RAII cad_tb_writer: the event file of one run (cad.h, "TensorBoard event files").  What the reference sends
+// to scripts/tensorboard_writer.py through tensorboard_logger_v2.h, written by the library itself.
+class EventWriter {
+public:
+    explicit EventWriter(const std::string& logdir) { cad::check(cad_tb_open(logdir.c_str(), &w_), "cad_tb_open"); }
+    ~EventWriter() { cad_tb_close(w_); }
+    EventWriter(const EventWriter&) = delete;
+    EventWriter& operator=(const EventWriter&) = delete;
+    std::string path() const { return cad_tb_path(w_); }
+    void flush() { cad::check(cad_tb_flush(w_), "cad_tb_flush"); }
+    void scalar(const std::string& tag, float v, int64_t step) { cad::check(cad_tb_scalar(w_, tag.c_str(), v, step), "cad_tb_scalar"); }
+    void text(const std::string& tag, const std::string& body, int64_t step = 0) {
+        cad::check(cad_tb_text(w_, tag.c_str(), step, body.c_str()), "cad_tb_text");
+    }
+    // the reference's layout (tensorboard_trainer_enhanced.h, the tags of its own event files)
+    void reference_layout() {
+        static const char* const rows[][3] = {
+            {"Training", "Loss", "loss/train"}, {"Training", "Loss", "loss/val"},
+            {"Training", "Loss Components", "loss_components/si_loss"}, {"Training", "Loss Components", "loss_components/grad_loss"},
+            {"Training", "Loss Components", "loss_components/smooth_loss"},
+            {"Training", "Loss Components", "loss_components/reproj_loss"}, {"Training", "Learning Rate", "training/lr"},
+            {"Metrics", "Relative Error", "metrics/abs_rel"}, {"Metrics", "Relative Error", "metrics/sq_rel"},
+            {"Metrics", "RMSE", "metrics/rmse"}, {"Metrics", "RMSE", "metrics/rmse_log"}, {"Metrics", "Accuracy", "metrics/a1"},
+            {"Metrics", "Accuracy", "metrics/a2"}, {"Metrics", "Accuracy", "metrics/a3"}, {"Model", "Gradients", "gradients/norm"},
+            {"Model", "Gradients", "gradients/max"}, {"Model", "Gradients", "gradients/min"}, {"Model", "Weights", "weights/norm"},
+            {"Model", "Weights", "weights/sparsity"}};
+        constexpr int n = (int)(sizeof rows / sizeof rows[0]);
+        const char *cat[n], *chart[n], *tag[n];
+        for (int i = 0; i < n; ++i) { cat[i] = rows[i][0]; chart[i] = rows[i][1]; tag[i] = rows[i][2]; }
+        cad::check(cad_tb_custom_scalars(w_, cat, chart, tag, n), "cad_tb_custom_scalars");
+    }
+    // logHyperparameters (:576-592): the sub-run with metric hparams/training = 0
+    void hparams(float lr, int batch_size, float weight_decay, float grad_clip_value, int num_epochs) {
+        const char* names[5] = {"learning_rate", "batch_size", "weight_decay", "grad_clip_value", "num_epochs"};
+        const double values[5] = {(double)lr, (double)batch_size, (double)weight_decay, (double)grad_clip_value, (double)num_epochs};
+        const char* metric = "hparams/training";
+        const float zero = 0.f;
+        cad::check(cad_tb_hparams(w_, names, values, 5, &metric, &zero, 1, nullptr), "cad_tb_hparams");
+    }
+    // logModelArchitecture (:593-615)
+    void architecture(int64_t total, int64_t trainable) {
+        std::stringstream a;
+        a << "# Model Architecture\n\n```\nTotal parameters: " << total << "\nTrainable parameters: " << trainable << "\n```\n";
+        text("model/architecture", a.str(), 0);
+    }
+    // one row of cad_hist_read: make_histogram's trimming, then the record
+    void histogram(const std::string& tag, int64_t step, const double* row, const uint32_t* counts) {
+        if (edges_.empty()) {
+            edges_.resize(CAD_HIST_BINS + 1);
+            cad_tb_default_bins(edges_.data(), (int)edges_.size());
+            lim_.resize(CAD_HIST_BINS + 1);
+            buc_.resize(CAD_HIST_BINS + 1);
+        }
+        int n = 0;
+        cad::check(cad_tb_trim_histogram(counts, CAD_HIST_BINS, edges_.data(), lim_.data(), buc_.data(), &n), "trim");
+        const double stats[5] = {row[1], row[2], row[0], row[3], row[4]};   // min, max, num, sum, sum_squares
+        cad::check(cad_tb_histogram(w_, tag.c_str(), step, stats, lim_.data(), buc_.data(), n), "cad_tb_histogram");
+    }
+    // an RGB8 image (h x w x 3, host) as a PNG image summary
+    void image(const std::string& tag, int64_t step, const uint8_t* rgb, int h, int w) {
+        int64_t cap = 0, size = 0;
+        cad::check(cad_png_encode(rgb, h, w, 3, 8, nullptr, 0, &cap), "cad_png_encode");
+        png_.resize((size_t)cap);
+        cad::check(cad_png_encode(rgb, h, w, 3, 8, png_.data(), cap, &size), "cad_png_encode");
+        cad::check(cad_tb_image(w_, tag.c_str(), step, h, w, 3, png_.data(), size), "cad_tb_image");
+    }
+
+private:
+    cad_tb_writer* w_ = nullptr;
+    std::vector<double> edges_, lim_, buc_;
+    std::vector<uint8_t> png_;
+};
+
+// predictions/sample_<i>: the exporter's rgb | gt | pred | error strip of one sample (composed on the device, as
+// build/predict's _panel.png), encoded and written as an image summary at step = epoch (visualizeResults, :444-470)
+class PanelLogger {
+public:
+    PanelLogger(int H, int W, int device) : H_(H), W_(W), ex_(1, H, W, device), host_((size_t)12 * H * W) {
+        void* p = nullptr;
+        cad::check(cad_malloc(device, (int64_t)host_.size(), &p), "panel buffer");
+        dev_ = static_cast<uint8_t*>(p);
+    }
+    ~PanelLogger() { cad_free(dev_); }
+    PanelLogger(const PanelLogger&) = delete;
+    PanelLogger& operator=(const PanelLogger&) = delete;
+    bool fits(int H, int W) const { return H == H_ && W == W_; }
+    // visualizeResults (:444-470): the first `ns` samples of the loader's unaugmented batch-1 ring, one at a time;
+    // next() fetches a sample into the trainer's buffers, forward() returns its prediction (device, H x W)
+    template <class Next, class Forward>
+    static void run(std::unique_ptr<PanelLogger>& self, EventWriter& ev, SunRGBDLoader& L, int device, int num_samples,
+                    int64_t epoch, const float* rgb, const float* gt, Next&& next, Forward&& forward) {
+        const int64_t ns = std::min<int64_t>(num_samples, (int64_t)L.size());
+        if (ns <= 0) return;
+        const int H = L.target_height(), W = L.target_width();
+        if (!self || !self->fits(H, W)) self = std::make_unique<PanelLogger>(H, W, device);
+        cad_loader* ring = L.ring(1, device, false);
+        cad::check(cad_loader_start_epoch(ring, nullptr, ns), "visualization");
+        for (int64_t i = 0; i < ns; ++i) {
+            next(ring);
+            self->log(ev, (int)i, epoch, rgb, gt, forward());
+        }
+    }
+    void log(EventWriter& ev, int sample, int64_t epoch, const float* rgb, const float* gt, const float* pred) {
+        ex_.comparison_panel(rgb, gt, pred, 1, CAD_CMAP_JET, dev_);
+        cad::check(cad_memcpy(host_.data(), dev_, (int64_t)host_.size(), 1, nullptr), "panel d2h");
+        ev.image("predictions/sample_" + std::to_string(sample), epoch, host_.data(), H_, 4 * W_);
+    }
+
+private:
+    int H_, W_;
+    cad::Exporter ex_;
+    uint8_t* dev_ = nullptr;
+    std::vector<uint8_t> host_;
+};
+
+// logWeightHistograms / logGradientStatistics (:506-555) for any network with a cad_*_histograms pass: weights/* and
+// gradients/* histograms of every parameter tensor (all elements, not the reference's 10 000 strided samples) into
+// `ev` when given, and the gradient pass's statistics as the reference's three scalars: norm = sqrt(sum of the
+// tensors' sum_squares), max starts at 0, min at FLT_MAX.  run(which, &hist) is the model's pass, name(i) the
+// i-th named_parameters() name.
+struct GradientStats {
+    double norm = 0.0;
+    float max = 0.f, min = std::numeric_limits<float>::max();
+};
+template <class Run, class Name>
+inline GradientStats log_histograms(EventWriter* ev, int num_params, int64_t epoch, Run&& run, Name&& name) {
+    std::vector<double> stats((size_t)num_params * CAD_HIST_STATS);
+    std::vector<uint32_t> counts(ev ? (size_t)num_params * CAD_HIST_BINS : 0);
+    GradientStats g;
+    double sq = 0.0;
+    for (int which = ev ? 0 : 1; which < 2; ++which) {
+        cad_hist* hh = nullptr;
+        cad::check(run(which, &hh), "histogram pass");
+        cad::check(cad_hist_read(hh, stats.data(), ev ? counts.data() : nullptr), "cad_hist_read");
+        for (int i = 0; i < num_params; ++i) {
+            const double* r = &stats[(size_t)i * CAD_HIST_STATS];   // num, min, max, sum, sum_squares, nonfinite
+            if (ev) {
+                std::string tag = std::string(which ? "gradients/" : "weights/") + name(i);
+                std::replace(tag.begin(), tag.end(), '.', '/');
+                ev->histogram(tag, epoch, r, &counts[(size_t)i * CAD_HIST_BINS]);
+            }
+            if (which == 1) {
+                sq += r[4];
+                if (r[0] > 0) { g.max = std::max(g.max, (float)r[2]); g.min = std::min(g.min, (float)r[1]); }
+            }
+        }
+    }
+    g.norm = std::sqrt(sq);
+    return g;
+}
 
 // .cadckpt: named parameters and buffers (reference layout) + the Adam state the reference never
 // saves (moments, step count) — a full resume.  torch::save archives (.pt) carry the weights only.
@@ -224,7 +382,7 @@ public:
         std::string tensorboard_dir = "./runs";
         std::string experiment_name = "experiment";
         int device = 0;              // torch::Device: the MI355X ordinal
-        bool tensorboard = true;     // write <log_dir>/tensorboard_scalars.csv
+        bool tensorboard = true;     // event files under <tensorboard_dir>/<experiment_name> + <log_dir>/tensorboard_scalars.csv
         bool save_optimizer = true;  // also write <name>_epoch_N.cadckpt next to each .pt
         int64_t bucket_elems = 25 << 18;   // data-parallel gradient buckets (25 MB)
     };
@@ -232,6 +390,18 @@ public:
     struct ValidationMetrics {   // enhanced.h:65-74
         float loss = 0.0f, abs_rel = 0.0f, sq_rel = 0.0f, rmse = 0.0f, rmse_log = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
     };
+    // the validation scalars of an epoch (:196-208), in the reference's order; shared with GeometryTrainer
+    template <class Scalar>
+    static void validationScalars(Scalar&& scalar, const ValidationMetrics& v) {
+        scalar("loss/val", v.loss);
+        scalar("metrics/abs_rel", v.abs_rel);
+        scalar("metrics/sq_rel", v.sq_rel);
+        scalar("metrics/rmse", v.rmse);
+        scalar("metrics/rmse_log", v.rmse_log);
+        scalar("metrics/a1", v.a1);
+        scalar("metrics/a2", v.a2);
+        scalar("metrics/a3", v.a3);
+    }
 
     // model and model_impl are the same network (the reference passes the Module and its Impl)
     TensorBoardTrainerEnhanced(std::shared_ptr<BaselineUNetImpl> model, std::shared_ptr<BaselineUNetImpl> model_impl,
@@ -252,10 +422,13 @@ public:
             if (config_.tensorboard) {
                 tb_.open(config_.log_dir + "/tensorboard_scalars.csv", std::ios::app);
                 if (tb_.tellp() == 0) tb_ << "tag,step,value\n";
+                // a new run or a resume opens a new event file (never appends); other ranks write nothing
+                events_ = std::make_unique<EventWriter>(config_.tensorboard_dir + "/" + config_.experiment_name);
             }
         }
         if (comm_) comm_->broadcast_parameters(*model_, 0);   // identical replicas
     }
+    const EventWriter* events() const { return events_.get(); }
 
     optim::Adam& optimizer() { return *optimizer_; }
     int64_t global_step() const { return global_step_; }
@@ -285,6 +458,12 @@ public:
                 << config_.grad_clip_value << "\nhparams/num_epochs,0," << config_.num_epochs
                 << "\nmodel/total_parameters,0," << model_->count_parameters() << "\n";
         }
+        if (events_) {
+            events_->reference_layout();
+            events_->hparams(config_.learning_rate, config_.batch_size, config_.weight_decay, config_.grad_clip_value, config_.num_epochs);
+            events_->architecture(model_->count_parameters(), model_->count_parameters());
+            events_->flush();
+        }
         const auto t0 = std::chrono::steady_clock::now();
         global_step_ = optimizer_->step_count() / nb * nb;
         for (int epoch = 1 + (int)(optimizer_->step_count() / nb); epoch <= config_.num_epochs; ++epoch) {
@@ -302,22 +481,18 @@ public:
             ValidationMetrics vm;
             if (lead() && val_loader && config_.val_interval > 0 && epoch % config_.val_interval == 0) {
                 vm = validateEpoch(*val_loader, epoch);
-                scalar("loss/val", vm.loss, epoch);
-                scalar("metrics/abs_rel", vm.abs_rel, epoch);
-                scalar("metrics/sq_rel", vm.sq_rel, epoch);
-                scalar("metrics/rmse", vm.rmse, epoch);
-                scalar("metrics/rmse_log", vm.rmse_log, epoch);
-                scalar("metrics/a1", vm.a1, epoch);
-                scalar("metrics/a2", vm.a2, epoch);
-                scalar("metrics/a3", vm.a3, epoch);
+                validationScalars([&](const char* tag, double v) { scalar(tag, v, epoch); }, vm);
             }
             if (lead() && config_.histogram_interval > 0 && epoch % config_.histogram_interval == 0)
                 logGradientStatistics(epoch);
+            if (lead() && events_ && config_.viz_interval > 0 && epoch % config_.viz_interval == 0)
+                visualizeResults(*train_loader, epoch);
             if (lead() && config_.save_interval > 0 && epoch % config_.save_interval == 0) saveCheckpoint(epoch);
             const long total = (long)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count();
             if (lead()) {
                 logEpochMetrics(epoch, (int)global_step_, train_loss, vm, total);
                 scalar("training/total_time_seconds", (double)total, epoch);
+                if (events_) events_->flush();
             }
             global_step_ += nb;   // :233
         }
@@ -326,6 +501,7 @@ public:
             if (config_.save_optimizer) saveTrainingState(config_.checkpoint_dir + "/final_model.cadckpt");
             logMessage("=== Training Complete ===");
         }
+        events_.reset();   // closed at the end of train() (and by the destructor)
     }
 
     // per-rank batches of an epoch: global batch bi = samples [bi*B*world, (bi+1)*B*world); with more
@@ -456,18 +632,30 @@ private:
         model_->train();
     }
 
-    void logGradientStatistics(int epoch) {   // :523-555 (scalars; no histograms)
+    // weights/* and gradients/* histograms from the device pass (log_histograms), and gradients/norm|max|min
+    // from its statistics instead of a host copy of every gradient
+    void logGradientStatistics(int epoch) {
         if (!tb_) return;
-        double norm = 0.0;
-        float mx = 0.f, mn = std::numeric_limits<float>::max();
-        for (const auto& g : model_->named_grads()) {
-            double s = 0.0;
-            for (float v : g.value) { s += (double)v * v; mx = std::max(mx, v); mn = std::min(mn, v); }
-            norm += s;
-        }
-        scalar("gradients/norm", std::sqrt(norm), epoch);
-        scalar("gradients/max", mx, epoch);
-        scalar("gradients/min", mn, epoch);
+        cad_unet* h = model_->handle();
+        const GradientStats g = log_histograms(
+            events_.get(), cad_unet_num_params(h), epoch, [&](int which, cad_hist** hh) { return cad_unet_histograms(h, which, nullptr, hh); },
+            [&](int i) {
+                const char* name = nullptr;
+                cad::check(cad_unet_tensor_info(h, 0, i, &name, nullptr, nullptr), "tensor_info");
+                return std::string(name);
+            });
+        scalar("gradients/norm", g.norm, epoch);
+        scalar("gradients/max", g.max, epoch);
+        scalar("gradients/min", g.min, epoch);
+    }
+
+    // predictions/sample_<i> panels (PanelLogger::run); train mode is restored after them
+    void visualizeResults(SunRGBDLoader& L, int epoch) {
+        ensure_buffers(L);
+        model_->eval();
+        PanelLogger::run(panels_, *events_, L, config_.device, config_.num_viz_samples, epoch, rgb_.data, gt_.data,
+                         [&](cad_loader* ring) { next(ring, 1); }, [&] { forward(); return (const float*)pred_.data; });
+        model_->train();
     }
 
     void logEpochMetrics(int epoch, int step, float train_loss, const ValidationMetrics& v, long elapsed) {   // :620-651
@@ -493,6 +681,7 @@ private:
 
     void scalar(const std::string& tag, double v, int64_t step) {
         if (tb_) tb_ << tag << "," << step << "," << v << "\n";
+        if (events_) events_->scalar(tag, (float)v, step);
     }
     void logMessage(const std::string& msg) {   // :667-682
         if (!lead()) return;
@@ -514,6 +703,8 @@ private:
     int rank_ = 0, world_ = 1;
     int64_t global_step_ = 0;
     std::ofstream train_log_, metrics_csv_, tb_;
+    std::unique_ptr<EventWriter> events_;   // lead rank with config.tensorboard only
+    std::unique_ptr<PanelLogger> panels_;
     DeviceTensor rgb_, gt_, K_, pred_, cam_;
 };
 
@@ -535,6 +726,7 @@ public:
         metrics_csv_.open(config_.log_dir + "/metrics.csv", std::ios::app);
         if (metrics_csv_.tellp() == 0)
             metrics_csv_ << "epoch,step,train_loss,val_loss,abs_rel,sq_rel,rmse,rmse_log,a1,a2,a3,learning_rate,time_elapsed\n";
+        if (config_.tensorboard) events_ = std::make_unique<EventWriter>(config_.tensorboard_dir + "/" + config_.experiment_name);
     }
 
     void train(std::shared_ptr<SunRGBDLoader> train_loader, std::shared_ptr<SunRGBDLoader> val_loader = nullptr) {
@@ -545,13 +737,26 @@ public:
         msg("=== Starting Training (MI355X, geometry-aware network) ===");
         msg("Train samples: " + std::to_string(train_loader->size()) + ", batch size " + std::to_string(B) +
             ", epochs " + std::to_string(config_.num_epochs));
+        if (events_) {
+            events_->reference_layout();
+            events_->hparams(config_.learning_rate, config_.batch_size, config_.weight_decay, config_.grad_clip_value, config_.num_epochs);
+            events_->architecture(model_->count_parameters(), model_->count_parameters());
+            events_->flush();
+        }
         const auto t0 = std::chrono::steady_clock::now();
         int64_t step = 0;
         for (int epoch = 1; epoch <= config_.num_epochs; ++epoch) {
             std::cout << "\n" << std::string(60, '=') << "\nEpoch " << epoch << "/" << config_.num_epochs << "\n";
             const float tl = trainEpoch(*train_loader, nb, step);
             TensorBoardTrainerEnhanced::ValidationMetrics vm;
-            if (val_loader && config_.val_interval > 0 && epoch % config_.val_interval == 0) vm = validate(*val_loader);
+            scalar("loss/train", tl, epoch);
+            scalar("training/learning_rate", config_.learning_rate, epoch);
+            if (val_loader && config_.val_interval > 0 && epoch % config_.val_interval == 0) {
+                vm = validate(*val_loader);
+                TensorBoardTrainerEnhanced::validationScalars([&](const char* tag, double v) { scalar(tag, v, epoch); }, vm);
+            }
+            if (config_.histogram_interval > 0 && epoch % config_.histogram_interval == 0) logGradientStatistics(epoch);
+            if (events_ && config_.viz_interval > 0 && epoch % config_.viz_interval == 0) visualize(*train_loader, epoch);
             if (config_.save_interval > 0 && epoch % config_.save_interval == 0)
                 save(config_.checkpoint_dir + "/" + config_.experiment_name + "_epoch_" + std::to_string(epoch) +
                      ".cadckpt");
@@ -564,10 +769,13 @@ public:
                          << "," << vm.rmse << "," << vm.rmse_log << "," << vm.a1 << "," << vm.a2 << "," << vm.a3 << ","
                          << config_.learning_rate << "," << el << "\n";
             metrics_csv_.flush();
+            scalar("training/total_time_seconds", (double)el, epoch);
+            if (events_) events_->flush();
             step += nb;
         }
         save(config_.checkpoint_dir + "/final_model.cadckpt");
         msg("=== Training Complete ===");
+        events_.reset();
     }
 
     // named parameters and buffers in the .cadckpt layout (no optimizer section)
@@ -628,6 +836,7 @@ private:
             if (!std::isfinite(lv)) throw std::runtime_error("non-finite loss at step " + std::to_string(step0 + bi));
             total += (double)lv * n;
             seen += n;
+            if ((bi + 1) % std::max(1, config_.log_interval) == 0) scalar("batch_loss/train", lv, step0 + bi);
             if ((bi + 1) % std::max(1, config_.log_interval) == 0 || bi == nb - 1)
                 std::cout << "\r  [" << std::setw(3) << (100 * (bi + 1) / nb) << "%] Batch " << (bi + 1) << "/" << nb
                           << " | Loss: " << std::fixed << std::setprecision(4) << lv << std::flush;
@@ -658,6 +867,35 @@ private:
         model_->train();
         return m;
     }
+    // the panels of TensorBoardTrainerEnhanced::visualizeResults, with this family's forward
+    void visualize(SunRGBDLoader& L, int epoch) {
+        ensure(L);
+        model_->eval();
+        DeviceTensor pred;
+        PanelLogger::run(panels_, *events_, L, config_.device, config_.num_viz_samples, epoch, rgb_.data, gt_.data,
+                         [&](cad_loader* ring) { next(ring); },
+                         [&] { pred = model_->forward(rgb_, rays_, cam_); return (const float*)pred.data; });
+        model_->train();
+    }
+    // weights/*, gradients/* and gradients/norm|max|min as TensorBoardTrainerEnhanced::logGradientStatistics
+    void logGradientStatistics(int epoch) {
+        if (!events_) return;
+        cad_geonet* h = model_->handle();
+        const GradientStats g = log_histograms(
+            events_.get(), cad_geonet_num_tensors(h, 0), epoch,
+            [&](int which, cad_hist** hh) { return cad_geonet_histograms(h, which, nullptr, hh); },
+            [&](int i) {
+                const char* name = nullptr;
+                cad::check(cad_geonet_tensor_info(h, 0, i, &name, nullptr, nullptr), "tensor_info");
+                return std::string(name);
+            });
+        scalar("gradients/norm", g.norm, epoch);
+        scalar("gradients/max", g.max, epoch);
+        scalar("gradients/min", g.min, epoch);
+    }
+    void scalar(const std::string& tag, double v, int64_t step) {
+        if (events_) events_->scalar(tag, (float)v, step);
+    }
     void msg(const std::string& s) {
         std::cout << s << std::endl;
         if (log_.is_open()) { log_ << s << "\n"; log_.flush(); }
@@ -667,6 +905,8 @@ private:
     std::shared_ptr<CombinedDepthLoss> loss_fn_;
     Config config_;
     std::ofstream log_, metrics_csv_;
+    std::unique_ptr<EventWriter> events_;   // config.tensorboard only
+    std::unique_ptr<PanelLogger> panels_;
     DeviceTensor rgb_, gt_, K_, rays_, cam_;
 };
 
