@@ -13,7 +13,7 @@ from ._abi import LIB_PATH, CadError, header_functions, load as load_library  # 
 
 def __getattr__(name):
     # lazy: importing the package must not require torch / a GPU (CPU tests only check the ABI)
-    if name in ("BaselineUNet", "IntrinsicsConditionedUNet", "RayConditionedUNet", "CombinedDepthLoss", "Adam",
+    if name in ("BaselineUNet", "IntrinsicsConditionedUNet", "IntrinsicsAttentionUNet", "RayConditionedUNet", "CombinedDepthLoss", "Adam",
                 "Trainer", "Communicator", "save", "load", "clip_grad_norm_", "depth_metrics", "ray_directions", "camera_from_K",
                 "ResNetUNet", "GeometryAwareNetwork", "LightweightGeometryNetwork", "depth_metrics_full", "Evaluator",
                 "evaluate", "EVAL_KEYS", "valid_medians"):

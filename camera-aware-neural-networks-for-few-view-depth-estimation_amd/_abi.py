@@ -160,6 +160,7 @@ SIGNATURES = {
     "cad_geonet_debug_buffer": (I64, [P, C.c_char_p, FP, I64]),
     "cad_op_cbam": (I, [P, P, P, I, I, I, I, P, P, P, P]),
     "cad_op_pcl": (I, [P, P, P, P, I, I, I, I, P, P, P, P, P]),
+    "cad_op_cbam_head": (I, [P, I, P, P, P, P, P, F, P, I, I, I, I, I, P, P, P, P, P, P, FP, P]),
     "cad_unet_create_model": (I, [C.POINTER(UnetDesc), I, I, C.POINTER(P)]),
     "cad_unet_model": (I, [P]),
     "cad_unet_forward_cam": (I, [P, P, P, P, I, P]),

@@ -31,10 +31,14 @@ inline Config load_config(const yaml_lite::Node& y) {
         c.variant = m["variant"].as<std::string>("full");
         c.use_pcl = m["use_pcl"].as<bool>(true);
         c.use_attention = m["use_attention"].as<bool>(true);
-        if (c.architecture != "baseline_unet" && c.architecture != "intrinsics_unet" && c.architecture != "ray_film_unet" &&
+        // intrinsics_unet builds the FiLM-only model whatever use_attention says (existing configs and
+        // checkpoints keep their meaning); intrinsics_attention_unet is the reference's IntrinsicsAttentionUNet
+        if (c.architecture != "baseline_unet" && c.architecture != "intrinsics_unet" &&
+            c.architecture != "intrinsics_attention_unet" && c.architecture != "ray_film_unet" &&
             c.architecture != "geometry_aware")
             throw std::runtime_error("model.architecture '" + c.architecture +
-                                     "': this CLI evaluates baseline_unet, intrinsics_unet, ray_film_unet or geometry_aware");
+                                     "': this CLI evaluates baseline_unet, intrinsics_unet, intrinsics_attention_unet, "
+                                     "ray_film_unet or geometry_aware");
         if (c.architecture == "geometry_aware" && c.variant != "full" && c.variant != "lightweight")
             throw std::runtime_error("model.variant '" + c.variant + "': expected full or lightweight");
     }

@@ -301,6 +301,7 @@ int run(const Args& a) {
     } else {
         std::shared_ptr<BaselineUNetImpl> m;
         if (c.architecture == "intrinsics_unet") m = std::make_shared<IntrinsicsConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
+        else if (c.architecture == "intrinsics_attention_unet") m = std::make_shared<IntrinsicsAttentionUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
         else if (c.architecture == "ray_film_unet") m = std::make_shared<RayConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
         else m = std::make_shared<BaselineUNetImpl>(3, c.init_features, c.max_depth, ws);
         if (pt) load(*m, a.checkpoint);

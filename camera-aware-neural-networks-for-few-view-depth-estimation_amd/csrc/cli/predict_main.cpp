@@ -310,6 +310,7 @@ int run(Args a) {
         gnet->eval();
     } else {
         if (c.architecture == "intrinsics_unet") unet = std::make_shared<IntrinsicsConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
+        else if (c.architecture == "intrinsics_attention_unet") unet = std::make_shared<IntrinsicsAttentionUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
         else if (c.architecture == "ray_film_unet") unet = std::make_shared<RayConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
         else unet = std::make_shared<BaselineUNetImpl>(3, c.init_features, c.max_depth, ws);
         if (pt) load(*unet, a.checkpoint);

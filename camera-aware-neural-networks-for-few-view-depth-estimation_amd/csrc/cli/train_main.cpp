@@ -177,10 +177,15 @@ Config load_config(const yaml_lite::Node& y, const std::string& experiment) {   
         // the reference parses model.architecture and always builds BaselineUNet; here it selects the
         // FiLM models of configs 3 (intrinsics_unet: FiLM blocks; ray_film_unet: + ray-enhanced enc1)
         c.architecture = m["architecture"].as<std::string>("baseline_unet");
-        if (c.architecture != "baseline_unet" && c.architecture != "intrinsics_unet" && c.architecture != "ray_film_unet" &&
+        // intrinsics_unet builds the FiLM-only model whatever use_attention says (existing configs and
+        // checkpoints keep their meaning); intrinsics_attention_unet is the reference's IntrinsicsAttentionUNet,
+        // the model its createModel picks for intrinsics_unet + use_attention: true
+        if (c.architecture != "baseline_unet" && c.architecture != "intrinsics_unet" &&
+            c.architecture != "intrinsics_attention_unet" && c.architecture != "ray_film_unet" &&
             c.architecture != "geometry_aware")
             throw std::runtime_error("model.architecture '" + c.architecture +
-                                     "': this CLI trains baseline_unet, intrinsics_unet, ray_film_unet or geometry_aware");
+                                     "': this CLI trains baseline_unet, intrinsics_unet, intrinsics_attention_unet, "
+                                     "ray_film_unet or geometry_aware");
         // geometry_aware (train_config.yaml:51-57 and its experiments): model.variant full /
         // lightweight, use_pcl, use_attention (GeometryAwareNetworkImpl / LightweightGeometryNetworkImpl)
         c.variant = m["variant"].as<std::string>("full");
@@ -491,6 +496,8 @@ int run(const Args& args) {
     std::shared_ptr<BaselineUNetImpl> model;
     if (c.architecture == "intrinsics_unet")
         model = std::make_shared<IntrinsicsConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
+    else if (c.architecture == "intrinsics_attention_unet")
+        model = std::make_shared<IntrinsicsAttentionUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
     else if (c.architecture == "ray_film_unet")
         model = std::make_shared<RayConditionedUNetImpl>(3, c.init_features, 4, c.max_depth, ws);
     else

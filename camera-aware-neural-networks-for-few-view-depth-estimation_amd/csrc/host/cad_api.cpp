@@ -86,12 +86,14 @@ struct Arena {
     float* f(int64_t n) { return static_cast<float*>(take(sizeof(float) * (size_t)std::max<int64_t>(n, 1))); }
     double* d(int64_t n) { return static_cast<double*>(take(sizeof(double) * (size_t)std::max<int64_t>(n, 1))); }
     uint8_t* u8(int64_t n) { return static_cast<uint8_t*>(take((size_t)std::max<int64_t>(n, 1))); }
+    int* i(int64_t n) { return static_cast<int*>(take(sizeof(int) * (size_t)std::max<int64_t>(n, 1))); }
 };
 
 enum PKind {
     P_CONV3, P_BNW, P_BNB, P_CONVT_W, P_CONVT_B, P_HEAD_W, P_HEAD_B,
     P_FC_W, P_FC_B,                                  // FiLM fc1 / fc2 (torch::nn::Linear defaults)
-    P_FILM_HEAD_W, P_FILM_GAMMA_B, P_FILM_BETA_B     // fc_gamma / fc_beta (film_layer.h:68-71)
+    P_FILM_HEAD_W, P_FILM_GAMMA_B, P_FILM_BETA_B,    // fc_gamma / fc_beta (film_layer.h:68-71)
+    P_SCONV                                          // CBAM spatial conv (1, 2, 7, 7), Conv2d defaults
 };
 
 struct PInfo {
@@ -190,6 +192,18 @@ struct cad_unet {
     DoubleConv dec[4];   // dec1..dec4 at levels 0..3 (index = level)
     Up up[4];            // dec_l.up: level l+1 -> l
     int head_w = -1, head_b = -1;
+    // CAD_MODEL_INTRINSICS_ATTN: att_{l+1} = CBAM(C_l) after decoder level l (intrinsics_unet.h:328-331).
+    // att_p0[l]: index of its channel_attention.fc1.weight, the five parameters follow in registration
+    // order; att[l]: its state (the parameter pointers are filled per use: the slabs may move)
+    int att_p0[4] = {-1, -1, -1, -1};
+    cad::Cbam att[4];
+    float* zatt[4] = {};          // dec_l's output relu(bn2(y2)), the CBAM input (level 0: only when not fused)
+    float* Sd = nullptr;          // [M_0][C_0] gradient on the other side of a CBAM from Sa
+    float *hq = nullptr, *hdp = nullptr;   // [M_0] the fused level-0 attention head's q and dL/dlogit
+    // the last forward ran level 0 as the fused attention head (cbam_head_fwd): dec1's output, att1's output
+    // and the head's input gradient are never written
+    bool att_head_fused = false;
+    bool attn() const { return model == CAD_MODEL_INTRINSICS_ATTN; }
     // activations
     float* x0 = nullptr;
     float* cat[4] = {};
@@ -308,6 +322,29 @@ void add_double_conv(cad_unet* h, DoubleConv& dc, const std::string& pre, int ci
     dc.last_param = (int)h->params.size() - 1;
 }
 
+// CAD_MODEL_INTRINSICS_ATTN: the slab keeps att_{l+1} right behind dec_{l+1}, whose backward stage
+// writes its gradients, so that every stage's gradients stay one contiguous range (the data-parallel
+// exchange sends a stage's range when the stage returns).  The parameter table itself — names, state
+// dicts, checkpoints — keeps the reference's registration order, att4 .. att1 after dec1.
+void assign_attn_slab_offsets(cad_unet* h) {
+    std::vector<int> order;
+    for (int i = 0; i < h->dec[3].first_param; ++i) order.push_back(i);
+    for (int l = 3; l >= 0; --l) {
+        for (int i = h->dec[l].first_param; i <= h->dec[l].last_param; ++i) order.push_back(i);
+        for (int j = 0; j < 5; ++j) order.push_back(h->att_p0[l] + j);
+    }
+    order.push_back(h->head_w);
+    order.push_back(h->head_b);
+    if (order.size() != h->params.size()) throw std::runtime_error("internal: attention slab order misses a parameter");
+    int64_t off = 0;
+    for (int i : order) {
+        off = (off + 63) & ~int64_t(63);
+        h->params[i].off = off;
+        off += h->params[i].n_int;
+    }
+    h->n_flat = (off + 63) & ~int64_t(63);
+}
+
 void build_tables(cad_unet* h) {
     const int f = h->f;
     // enc1.conv1 runs on 8 internal input channels (zero-padded weights and input): the pre-split
@@ -330,11 +367,24 @@ void build_tables(cad_unet* h) {
         add_double_conv(h, h->dec[l], pre + "conv.", cin, cin, cout, l);
         h->dec[l].first_param = h->up[l].widx;
     }
+    if (h->attn()) {   // att4 .. att1 (intrinsics_unet.h:328-331); CBAMImpl(C) (spatial_attention.h:153-158)
+        for (int l = 3; l >= 0; --l) {
+            const int C = f << l, Cr = std::max(1, C / 16);
+            const std::string pre = "att" + std::to_string(l + 1) + ".";
+            h->att_p0[l] = (int)h->params.size();
+            add_param(h, pre + "channel_attention.fc1.weight", {Cr, C}, P_FC_W);
+            add_param(h, pre + "channel_attention.fc1.bias", {Cr}, P_FC_B);
+            add_param(h, pre + "channel_attention.fc2.weight", {C, Cr}, P_FC_W);
+            add_param(h, pre + "channel_attention.fc2.bias", {C}, P_FC_B);
+            add_param(h, pre + "spatial_attention.conv.weight", {1, 2, 7, 7}, P_SCONV);
+        }
+    }
     add_param(h, "out_conv.weight", {1, f, 1, 1}, P_HEAD_W);
     add_param(h, "out_conv.bias", {1}, P_HEAD_B);
     h->head_w = (int)h->params.size() - 2;
     h->head_b = (int)h->params.size() - 1;
     h->n_flat = (h->n_flat + 63) & ~int64_t(63);
+    if (h->attn()) assign_attn_slab_offsets(h);
 }
 
 void bn_alloc(Arena& a, BN& b) {
@@ -421,6 +471,24 @@ void layout(cad_unet* h, Arena& a) {
     h->Sb2 = a.f(M0C0);
     h->dYs2 = sp(h->Ml(0, B) * h->Cl(0));
     h->Sc = a.f(h->Ml(1, B) * h->Cl(0));
+    if (h->attn()) {   // all CBAM state lives here: nothing is allocated inside a step
+        h->Sd = a.f(M0C0);
+        for (int l = 0; l < 4; ++l) {
+            const int C = h->Cl(l), Cr = std::max(1, C / 16);
+            const int64_t M = h->Ml(l, B);
+            const bool fused = l == 0 && cad::head_fusable(C);
+            h->zatt[l] = fused ? nullptr : a.f(M * C);
+            cad::Cbam& A = h->att[l];
+            A.C = C; A.Cr = Cr;
+            A.avg = a.f((int64_t)B * C); A.mx = a.f((int64_t)B * C); A.amax = a.i((int64_t)B * C);
+            A.ha = a.f((int64_t)B * Cr); A.hm = a.f((int64_t)B * Cr); A.att = a.f((int64_t)B * C);
+            A.s = a.f(2 * M); A.sidx = a.i(M); A.sa = a.f(M);
+            A.dlog = a.f(M); A.ds = a.f(2 * M);
+            A.dO = a.f((int64_t)B * C); A.dha = a.f((int64_t)B * Cr); A.dhm = a.f((int64_t)B * Cr);
+            A.dva = a.f((int64_t)B * C); A.dvm = a.f((int64_t)B * C);
+            if (fused) { h->hq = a.f(M); h->hdp = a.f(M); }
+        }
+    }
     // BN tile partials: rows x (2C + 1) (S, M2 per channel + the row's count), max over layers
     int64_t st = 0, colmax = 0;
     for (int l = 0; l < 5; ++l) {
@@ -432,6 +500,8 @@ void layout(cad_unet* h, Arena& a) {
     int64_t dscr = (int64_t)(cad::colsum_slices(h->Ml(0, B)) + 2) * 4 * colmax + 4 * colmax + 8192;
     for (int l = 0; l < 5 && film; ++l)
         dscr = std::max(dscr, cad::film_reduce_doubles(B, (int64_t)h->Hl(l) * h->Wl(l), h->Cl(l)) + 8192);
+    for (int l = 0; l < 4 && h->attn(); ++l)
+        dscr = std::max(dscr, cad::cbam_head_scratch_doubles(B, (int64_t)h->Hl(l) * h->Wl(l), h->Cl(l)) + 8192);
     h->dscr = a.d(dscr);
     h->dscr2 = a.d(dscr);
     // wgrad split-K slab: enough for the largest-benefit layers, capped at 64M floats (256 MB)
@@ -488,6 +558,27 @@ cad::FilmLayer film_view(const cad_unet* h, const DoubleConv& dc) {
     L.gwg = h->G(i + 4); L.gbg = h->G(i + 5); L.gwb = h->G(i + 6); L.gbb = h->G(i + 7);
     L.gg1 = h->G(i + 8); L.gbe1 = h->G(i + 9); L.gg2 = h->G(i + 10); L.gbe2 = h->G(i + 11);
     return L;
+}
+
+// att_{l+1}'s Cbam with the parameter / gradient pointers of the current slabs
+cad::Cbam cbam_view(const cad_unet* h, int l) {
+    cad::Cbam A = h->att[l];
+    const int i = h->att_p0[l];
+    A.w1 = h->P(i); A.b1 = h->P(i + 1); A.w2 = h->P(i + 2); A.b2 = h->P(i + 3); A.wsp = h->P(i + 4);
+    A.gw1 = h->G(i); A.gb1 = h->G(i + 1); A.gw2 = h->G(i + 2); A.gb2 = h->G(i + 3); A.gwsp = h->G(i + 4);
+    return A;
+}
+// the fused level-0 attention head's operands (dec1's bn2 coefficients are those of the last forward)
+cad::CbamHead cbam_head_view(const cad_unet* h) {
+    const DoubleConv& d = h->dec[0];
+    cad::CbamHead Hd;
+    Hd.y = d.y2; Hd.y_bf16 = d.y2b;
+    Hd.scale = d.b2.scale; Hd.shift = d.b2.shift;
+    Hd.w = h->P(h->head_w); Hd.b = h->P(h->head_b);
+    Hd.md = h->max_depth;
+    Hd.q = h->hq; Hd.sig = h->sig; Hd.dp = h->hdp;
+    Hd.gw = h->G(h->head_w); Hd.gb = h->G(h->head_b);
+    return Hd;
 }
 
 // pre-split operands (gemm_ps.hpp) are used when the engine splits (S3 / B1) and the operand's
@@ -556,10 +647,11 @@ bool bn_pool_on() {
 
 // head_pred != nullptr: the block's bn2 + ReLU feeds the depth head directly (level-0 fusion): sig
 // and head_pred are written, out is not.  pool != nullptr: the block's bn2 pass also writes the next
-// level's max-pool
+// level's max-pool.  att_head (with head_pred): the head is the fused attention head, CBAM between the
+// block and out_conv (cbam_head_fwd)
 void double_conv_fwd(cad_unet* h, DoubleConv& dc, const float* in, int64_t ldin, cad::Split in_s, int B, float* out,
                      int64_t ldo, int ocoff, cad::Split out_s, hipStream_t st, bool out_f32 = true,
-                     float* head_pred = nullptr, const PoolOut* pool = nullptr) {
+                     float* head_pred = nullptr, const PoolOut* pool = nullptr, bool att_head = false) {
     const int l = dc.level, Hh = h->Hl(l), Ww = h->Wl(l), C = dc.c1.cout;
     const int64_t M = h->Ml(l, B);
     const bool tr = h->train;
@@ -599,6 +691,10 @@ void double_conv_fwd(cad_unet* h, DoubleConv& dc, const float* in, int64_t ldin,
     else
         cad::conv3x3_fwd(dc.a1, C, 0, C, h->P(dc.c2.pidx), C, dc.y2, C, 0, B, Hh, Ww, stats, st);
     bn(dc.b2, C, ps);
+    if (head_pred && att_head) {
+        cad::cbam_head_fwd(cbam_view(h, 0), cbam_head_view(h), B, Hh, Ww, head_pred, h->dscr, st);
+        return;
+    }
     if (head_pred) {
         cad::bn_relu_head_fwd(dc.y2, C, dc.b2.scale, dc.b2.shift, h->P(h->head_w), h->P(h->head_b), h->max_depth, h->sig,
                               head_pred, M, st, dc.y2b);
@@ -692,7 +788,11 @@ void unet_forward(cad_unet* h, const float* rgb, const float* cam4, float* depth
                             false);
         }
     }
-    h->head_fused = head_fusion_on() && cad::head_fusable(f);
+    // the attention model's level 0 is fused whenever its channel count allows (no switch); the baseline's
+    // head fusion does not apply to it (a CBAM sits between dec1 and out_conv)
+    const bool attn = h->attn();
+    h->head_fused = !attn && head_fusion_on() && cad::head_fusable(f);
+    h->att_head_fused = attn && cad::head_fusable(f);
     for (int l = 3; l >= 0; --l) {
         const float* upin = l == 3 ? h->a2_bott : h->dout[l + 1];
         const void* upins = l == 3 ? h->botts : h->douts[l + 1];
@@ -705,10 +805,24 @@ void unet_forward(cad_unet* h, const float* rgb, const float* cam4, float* depth
             cad::convT_fwd(upin, u.cin, u.cin, u.wf, h->P(u.bidx), u.cout, h->cat[l], 2 * C, C, B, h->Hl(l + 1),
                            h->Wl(l + 1), st);
         }
+        if (attn) {
+            // dec_{l+1} then att_{l+1} (intrinsics_unet.h:352-362).  The tensors on either side of a CBAM are
+            // fp32 on every engine: the block's bn2 pass writes z, cbam_fwd the attended tensor, and the
+            // next ConvT's operand twin is split from that
+            if (l == 0 && h->att_head_fused) {
+                double_conv_fwd(h, h->dec[0], h->cat[0], 2 * C, sv(h->cats[0], 2 * C), B, nullptr, C, 0, none, st, true,
+                                depth, nullptr, true);
+                continue;
+            }
+            double_conv_fwd(h, h->dec[l], h->cat[l], 2 * C, sv(h->cats[l], 2 * C), B, h->zatt[l], C, 0, none, st, true);
+            cad::cbam_fwd(cbam_view(h, l), h->zatt[l], B, h->Hl(l), h->Wl(l), h->dout[l], C, 0, h->dscr, st);
+            if (ps && l > 0) cad::split_rows(h->dout[l], C, 0, C, h->Ml(l, B), h->douts[l], C, 0, st);
+            continue;
+        }
         double_conv_fwd(h, h->dec[l], h->cat[l], 2 * C, sv(h->cats[l], 2 * C), B, h->dout[l], C, 0,
                         l > 0 ? sv(h->douts[l], C) : none, st, l == 0, l == 0 && h->head_fused ? depth : nullptr);
     }
-    if (!h->head_fused)
+    if (!h->head_fused && !h->att_head_fused)
         cad::head_fwd(h->dout[0], f, h->P(h->head_w), h->P(h->head_b), h->max_depth, h->sig, depth, h->Ml(0, B), st);
 }
 
@@ -867,6 +981,18 @@ void backward_stage_body(cad_unet* h, int stage, const float* dpred, hipStream_t
         HIPCHK(hipEventRecord(h->evA, st));
         HIPCHK(hipEventRecord(h->evB, st));
         repack_dgrad_weights(h, st);
+        if (h->attn()) {
+            // the head's and att1's gradients, and dL/d(dec1 output) into Sa.  att1's range belongs to
+            // stage 1 (with dec1): written here, complete before stage 1 returns
+            if (h->att_head_fused) {
+                cad::cbam_head_bwd(cbam_view(h, 0), cbam_head_view(h), dpred, B, h->H, h->W, h->Sa, h->dscr, st);
+            } else {
+                cad::head_bwd(h->dout[0], f, h->P(h->head_w), dpred, h->sig, h->max_depth, h->Sd, h->Ml(0, B), h->dscr,
+                              h->G(h->head_w), h->G(h->head_b), st);
+                cad::cbam_bwd(cbam_view(h, 0), h->zatt[0], h->Sd, f, 0, B, h->H, h->W, h->Sa, h->dscr, st);
+            }
+            return;
+        }
         if (h->head_fused) {   // head weight / bias gradient from dec1's bn2 input; its input gradient: stage 1
             const DoubleConv& d = h->dec[0];
             cad::head_bwd_y(d.y2, f, d.b2.scale, d.b2.shift, dpred, h->sig, h->max_depth, h->Ml(0, B), h->dscr,
@@ -889,10 +1015,19 @@ void backward_stage_body(cad_unet* h, int stage, const float* dpred, hipStream_t
         const bool split = ps && dcat_split_on() &&
                            cad::conv3x3_dgrad_split_ok(sv(h->dYs, C), C, sv(h->dec[l].c1.wds, 9 * C), 2 * C, h->Wl(l), C);
         bool up_twin = false;
+        // the attention model: Sa holds the gradient of att_{l+1}'s output (fp32 on every engine); above
+        // level 0 cbam_bwd runs ahead of the block's backward, on this stream, and leaves the block-output
+        // gradient in Sd (level 0: stage 0 left it in Sa)
+        const bool attn = h->attn();
+        const float* g = h->Sa;
+        if (attn && l > 0) {
+            cad::cbam_bwd(cbam_view(h, l), h->zatt[l], h->Sa, C, 0, B, h->Hl(l), h->Wl(l), h->Sd, h->dscr, st);
+            g = h->Sd;
+        }
         // above level 0 the block-output gradient in Sa comes from the ConvT dgrad: bf16 on the bf16 engine
-        double_conv_bwd(h, h->dec[l], hf ? nullptr : h->Sa, C, 0, h->cat[l], 2 * C, sv(h->cats[l], 2 * C), B,
+        double_conv_bwd(h, h->dec[l], hf ? nullptr : g, C, 0, h->cat[l], 2 * C, sv(h->cats[l], 2 * C), B,
                         split ? static_cast<float*>(h->dskips[l]) : h->dcat[l], split ? C : 2 * C, st,
-                        hf ? &hg : nullptr, nullptr, split ? h->dcats[l] : nullptr, &up_twin, ps && l > 0, split);
+                        hf ? &hg : nullptr, nullptr, split ? h->dcats[l] : nullptr, &up_twin, ps && l > 0 && !attn, split);
         if (split != up_twin) throw std::runtime_error("decoder dgrad split store not taken");
         const Up& u = h->up[l];
         const float* upin = l == 3 ? h->a2_bott : h->dout[l + 1];
@@ -916,8 +1051,9 @@ void backward_stage_body(cad_unet* h, int stage, const float* dpred, hipStream_t
         else cad::colsum(h->dcat[l], 2 * C, C, h->Ml(l, B), C, h->dscr2, sd);
         cad::colsum_finalize(h->dscr2, cad::colsum_slices(h->Ml(l, B)), C, h->G(u.bidx), 1.f, sd);
         if (ps)
+            // (fp32 into a CBAM's backward; the bottleneck's bn2 backward reads bf16)
             cad::convT_dgrad_ps(sv(h->dcats[l], C), u.cout, sv(u.wms, 4 * u.cout), u.cin, h->Sa, B, h->Hl(l + 1),
-                                h->Wl(l + 1), st, true);
+                                h->Wl(l + 1), st, !(attn && l < 3));
         else
             cad::convT_dgrad(h->dcat[l], 2 * C, C, u.cout, h->P(u.widx), u.cin, h->Sa, B, h->Hl(l + 1), h->Wl(l + 1), st);
         return;
@@ -959,8 +1095,17 @@ void compute_stage_ranges(cad_unet* h) {
     };
     h->stage_range.clear();
     h->stage_range.push_back(rng(h->head_w, h->head_b));
-    for (int l = 0; l < 4; ++l) h->stage_range.push_back(rng(h->dec[l].first_param, h->dec[l].last_param));
+    // (the attention model's slab keeps att_{l+1} behind dec_{l+1}: assign_attn_slab_offsets)
+    for (int l = 0; l < 4; ++l)
+        h->stage_range.push_back(rng(h->dec[l].first_param, h->attn() ? h->att_p0[l] + 4 : h->dec[l].last_param));
     for (int l = 4; l >= 0; --l) h->stage_range.push_back(rng(h->enc[l].first_param, h->enc[l].last_param));
+    // every parameter lies in exactly one stage's range
+    for (const PInfo& p : h->params) {
+        int n = 0;
+        for (const auto& r : h->stage_range) n += p.off >= r.first && p.off + p.n_int <= r.first + r.second;
+        if (n != 1) throw std::runtime_error("internal: parameter '" + p.name + "' is covered by " + std::to_string(n) +
+                                             " backward stages");
+    }
 }
 
 // reference layout <-> internal layout
@@ -1021,6 +1166,7 @@ void default_init(cad_unet* h) {
         } else {
             int64_t fan_in;
             if (p.kind == P_CONV3) fan_in = (int64_t)p.cin_ref * 9;
+            else if (p.kind == P_SCONV) fan_in = 2 * 49;
             else if (p.kind == P_CONVT_W || p.kind == P_CONVT_B) {
                 const PInfo& w = p.kind == P_CONVT_W ? p : h->params[&p - &h->params[0] - 1];
                 fan_in = w.shape[1] * 4;
@@ -1091,7 +1237,8 @@ cad_status cad_unet_create(const cad_unet_desc* d, int device, cad_unet** out) {
 cad_status cad_unet_create_model(const cad_unet_desc* d, int model, int device, cad_unet** out) {
     return guard([&] {
         require(d && out, "null argument");
-        require(model == CAD_MODEL_BASELINE || model == CAD_MODEL_INTRINSICS_FILM || model == CAD_MODEL_RAY_FILM,
+        require(model == CAD_MODEL_BASELINE || model == CAD_MODEL_INTRINSICS_FILM || model == CAD_MODEL_RAY_FILM ||
+                    model == CAD_MODEL_INTRINSICS_ATTN,
                 "unknown model kind");
         require(d->in_channels == 3, "in_channels must be 3 (rgb)");
         require(d->init_features >= 4 && d->init_features % 4 == 0, "init_features must be a multiple of 4");
@@ -1283,8 +1430,18 @@ int64_t cad_unet_debug_buffer(cad_unet* h, const char* name, float* host, int64_
         }
     }
     else if (n == "camn") { p = h->camn; cnt = (int64_t)B * 4; }
+    if (h->attn()) {   // att_{l+1}'s state of the last forward (amax / sidx: int32, bit-copied)
+        if ((l = lvl("att")) >= 0 && l < 4) { p = h->att[l].att; cnt = (int64_t)B * h->Cl(l); }
+        else if ((l = lvl("sa")) >= 0 && l < 4) { p = h->att[l].sa; cnt = h->Ml(l, B); }
+        else if ((l = lvl("amax")) >= 0 && l < 4) { p = reinterpret_cast<const float*>(h->att[l].amax); cnt = (int64_t)B * h->Cl(l); }
+        else if ((l = lvl("sidx")) >= 0 && l < 4) { p = reinterpret_cast<const float*>(h->att[l].sidx); cnt = h->Ml(l, B); }
+    }
     if (!p || cnt < 0) {
         g_err = "unknown debug buffer '" + n + "'";
+        return -1;
+    }
+    if (n == "dout0" && h->att_head_fused) {
+        g_err = "debug buffer 'dout0' is not written when level 0 runs the fused attention head";
         return -1;
     }
     if (n == "dout0" && h->head_fused) {
@@ -1296,7 +1453,7 @@ int64_t cad_unet_debug_buffer(cad_unet* h, const char* name, float* host, int64_
     if (h->fwd_np > 0) {
         const bool twin_only = n == "Sb" || n == "bott" || (n.compare(0, 4, "pool") == 0) ||
                                (n.compare(0, 3, "cat") == 0) ||   // up half: twin only
-                               (n.compare(0, 4, "dout") == 0 && n != "dout0") ||
+                               (n.compare(0, 4, "dout") == 0 && n != "dout0" && !h->attn()) ||
                                (n.size() > 5 && n.substr(5) == "a1");
         if (twin_only) {
             g_err = "debug buffer '" + n + "' holds no fp32 copy on the pre-split (bf16) engine";
@@ -1362,6 +1519,14 @@ cad_status cad_unet_save_torch(cad_unet* h, const char* path) {
                     entry(std::string(pooled[k]) + "pool", 2, CAD_DTYPE_F32, 0, nullptr, nullptr);
                     placed[k] = true;
                 }
+            // ChannelAttentionImpl registers its parameterless AdaptiveAvgPool2d / AdaptiveMaxPool2d
+            // ahead of fc1 (spatial_attention.h:41-42)
+            const std::string ca = "channel_attention.fc1.weight";
+            if (p.name.size() > ca.size() && p.name.compare(p.name.size() - ca.size(), ca.size(), ca) == 0) {
+                const std::string pre = p.name.substr(0, p.name.size() - std::string("fc1.weight").size());
+                entry(pre + "avg_pool", 2, CAD_DTYPE_F32, 0, nullptr, nullptr);
+                entry(pre + "max_pool", 2, CAD_DTYPE_F32, 0, nullptr, nullptr);
+            }
             data.emplace_back((size_t)p.n_ref);
             get_slab_tensor(h, h->flat_p, (int)i, data.back().data(), p.n_ref);
             entry(p.name, 0, CAD_DTYPE_F32, p.ndim, p.shape, data.back().data());
@@ -1445,6 +1610,25 @@ cad_status cad_unet_load_torch(cad_unet* h, const char* path) {
         std::unique_ptr<cad_archive, void (*)(cad_archive*)> a(raw, cad_archive_close);
         HIPCHK(hipSetDevice(h->device));
         HIPCHK(hipDeviceSynchronize());
+        // intrinsics_unet and intrinsics_attention_unet differ only by the att<k>.* tensors: a checkpoint of
+        // the other one is refused by name (loading by name alone would take its common part silently)
+        if (h->model == CAD_MODEL_INTRINSICS_FILM || h->attn()) {
+            const bool ck_attn = cad_archive_find(a.get(), "att1.spatial_attention.conv.weight") >= 0;
+            if (ck_attn != h->attn()) {
+                int64_t att = 0;
+                for (int l = 0; l < 4; ++l) {
+                    const int64_t C = h->Cl(l), Cr = std::max<int64_t>(1, C / 16);
+                    att += 2 * C * Cr + C + Cr + 98;
+                }
+                const int64_t mine = cad_unet_count_parameters(h), other = h->attn() ? mine - att : mine + att;
+                throw CadError(CAD_ERR_INVALID,
+                               std::string("checkpoint '") + path + "' holds " + (ck_attn ? "intrinsics_attention_unet" : "intrinsics_unet") +
+                                   " (" + std::to_string(other) + " parameters), this model is " +
+                                   (h->attn() ? "intrinsics_attention_unet" : "intrinsics_unet") + " (" + std::to_string(mine) +
+                                   " parameters): set model.architecture: " +
+                                   (ck_attn ? "intrinsics_attention_unet" : "intrinsics_unet") + " to load it");
+            }
+        }
         auto find = [&](const std::string& name, int ndim, const int64_t* shape) {
             const int i = cad_archive_find(a.get(), name.c_str());
             require(i >= 0, "checkpoint has no '" + name + "'");
@@ -1527,7 +1711,8 @@ int cad_unet_num_stages(const cad_unet*) { return kStages; }
 cad_status cad_model_grad_layout(int model, int in_channels, int init_features, int* nstages, int64_t stage_off[16],
                                  int64_t stage_cnt[16], int64_t* n_flat) {
     return guard([&] {
-        require(model == CAD_MODEL_BASELINE || model == CAD_MODEL_INTRINSICS_FILM || model == CAD_MODEL_RAY_FILM,
+        require(model == CAD_MODEL_BASELINE || model == CAD_MODEL_INTRINSICS_FILM || model == CAD_MODEL_RAY_FILM ||
+                    model == CAD_MODEL_INTRINSICS_ATTN,
                 "unknown model kind");
         require(in_channels == 3 && init_features >= 4 && init_features % 4 == 0, "bad model description");
         cad_unet t;   // tables only: no device memory is touched

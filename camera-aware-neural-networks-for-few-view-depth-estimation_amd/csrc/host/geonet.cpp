@@ -962,6 +962,90 @@ cad_status cad_op_cbam(const float* x, const float* g, const float* params, int 
     });
 }
 
+// Level 0 of the attention U-Net on caller tensors: the fused attention head (fused = 1) or the generic
+// composition bn_relu_fwd, cbam_fwd, head_fwd, head_bwd, cbam_bwd (fused = 0)
+cad_status cad_op_cbam_head(const float* y, int y_bf16, const float* scale, const float* shift, const float* cbam_params,
+                            const float* head_w, const float* head_b, float max_depth, const float* dpred, int B, int H,
+                            int W, int C, int fused, float* pred, float* dz, float* cbam_grads, float* head_grads,
+                            int* sidx_out, int* amax_out, float* elapsed_ms, void* stream) {
+    return gguard([&] {
+        need(y && scale && shift && cbam_params && head_w && head_b && dpred && pred && dz && cbam_grads && head_grads &&
+                 B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0,
+             "bad argument");
+        need(!fused || cad::head_fusable(C), "the fused attention head needs C / 4 a power of two <= 32");
+        const int Cr = std::max(1, C / 16);
+        const int64_t M = (int64_t)B * H * W, HW = (int64_t)H * W;
+        Arena sz, real;
+        cad::Cbam A{};
+        cad::CbamHead Hd{};
+        float *z = nullptr, *out = nullptr, *g = nullptr;
+        auto lay = [&](Arena& a) {
+            A.C = C; A.Cr = Cr;
+            A.avg = a.f((int64_t)B * C); A.mx = a.f((int64_t)B * C); A.amax = a.i((int64_t)B * C);
+            A.ha = a.f((int64_t)B * Cr); A.hm = a.f((int64_t)B * Cr); A.att = a.f((int64_t)B * C);
+            A.s = a.f(2 * M); A.sidx = a.i(M); A.sa = a.f(M); A.dlog = a.f(M); A.ds = a.f(2 * M);
+            A.dO = a.f((int64_t)B * C); A.dha = a.f((int64_t)B * Cr); A.dhm = a.f((int64_t)B * Cr);
+            A.dva = a.f((int64_t)B * C); A.dvm = a.f((int64_t)B * C);
+            Hd.q = a.f(M); Hd.sig = a.f(M); Hd.dp = a.f(M);
+            if (!fused) { z = a.f(M * C); out = a.f(M * C); g = a.f(M * C); }
+            // (head_bwd's column reduction: cad_api.cpp's dscr sizing)
+            return a.d(std::max<int64_t>(cad::cbam_head_scratch_doubles(B, HW, C),
+                                         (int64_t)(cad::colsum_slices(M) + 2) * 4 * C + 4 * C + 8192));
+        };
+        lay(sz);
+        void* base = nullptr;
+        GCHK(hipMalloc(&base, sz.off + 4096));
+        real.base = static_cast<char*>(base);
+        double* scr = lay(real);
+        const int64_t o1 = (int64_t)Cr * C, o2 = o1 + Cr, o3 = o2 + (int64_t)C * Cr, o4 = o3 + C;
+        A.w1 = cbam_params; A.b1 = cbam_params + o1; A.w2 = cbam_params + o2; A.b2 = cbam_params + o3;
+        A.wsp = cbam_params + o4;
+        A.gw1 = cbam_grads; A.gb1 = cbam_grads + o1; A.gw2 = cbam_grads + o2; A.gb2 = cbam_grads + o3;
+        A.gwsp = cbam_grads + o4;
+        Hd.y = y; Hd.y_bf16 = y_bf16 != 0; Hd.scale = scale; Hd.shift = shift; Hd.w = head_w; Hd.b = head_b;
+        Hd.md = max_depth; Hd.gw = head_grads; Hd.gb = head_grads + C;
+        hipStream_t st = S(stream);
+        auto run = [&] {
+            if (fused) {
+                cad::cbam_head_fwd(A, Hd, B, H, W, pred, scr, st);
+                cad::cbam_head_bwd(A, Hd, dpred, B, H, W, dz, scr, st);
+            } else {
+                cad::bn_relu_fwd(y, C, scale, shift, z, C, 0, M, st, nullptr, 0, 0, y_bf16 != 0);
+                cad::cbam_fwd(A, z, B, H, W, out, C, 0, scr, st);
+                cad::head_fwd(out, C, head_w, head_b, max_depth, Hd.sig, pred, M, st);
+                cad::head_bwd(out, C, head_w, dpred, Hd.sig, max_depth, g, M, scr, Hd.gw, Hd.gb, st);
+                cad::cbam_bwd(A, z, g, C, 0, B, H, W, dz, scr, st);
+            }
+        };
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        try {
+            run();
+            if (elapsed_ms) {   // a second, identical run between two device events (the first one warmed up)
+                GCHK(hipEventCreate(&e0));
+                GCHK(hipEventCreate(&e1));
+                GCHK(hipEventRecord(e0, st));
+                run();
+                GCHK(hipEventRecord(e1, st));
+                GCHK(hipEventSynchronize(e1));
+                GCHK(hipEventElapsedTime(elapsed_ms, e0, e1));
+            }
+            if (sidx_out) (void)hipMemcpyAsync(sidx_out, A.sidx, sizeof(int) * M, hipMemcpyDeviceToDevice, st);
+            if (amax_out) (void)hipMemcpyAsync(amax_out, A.amax, sizeof(int) * B * C, hipMemcpyDeviceToDevice, st);
+        } catch (...) {
+            (void)hipStreamSynchronize(st);
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+            (void)hipFree(base);
+            throw;
+        }
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        (void)hipFree(base);
+        GCHK(e);
+    });
+}
+
 cad_status cad_op_pcl(const float* u, const float* camn, const float* g, const float* params, int B, int H, int W,
                       int C, float* out, float* du, float* grads, float* theta, void* stream) {
     return gguard([&] {

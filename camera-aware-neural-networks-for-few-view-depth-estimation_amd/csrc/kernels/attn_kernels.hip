@@ -17,7 +17,10 @@
 // gradient, a scatter (hardware fp32 atomics, like the reference's CUDA kernel); the reference's CPU
 // path adds serially, so that gradient agrees to rounding, not bit for bit.
 #include <algorithm>
+#include <stdexcept>
+#include <type_traits>
 
+#include "ew_load.hpp"
 #include "kernels.hpp"
 
 namespace cad {
@@ -436,6 +439,401 @@ void cbam_bwd(const Cbam& A, const float* x, const float* g, int64_t ldg, int gc
     const int64_t nw = 2 * (int64_t)C * A.Cr + C + A.Cr;
     hipLaunchKernelGGL(k_cbam_mlp_wgrad, dim3(cdiv(nw, 256)), dim3(256), 0, st, A, B);
     hipLaunchKernelGGL(k_cbam_dx, dim3(ew_blocks(M * C)), dim3(256), 0, st, A, g, ldg, gcoff, HW, dx, M * C);
+}
+
+// ------------------------------------------------------------------------------------------
+// Level-0 attention head of IntrinsicsAttentionUNetImpl, fused (kernels.hpp CbamHead)
+// ------------------------------------------------------------------------------------------
+// pred = md·σ(out_conv(CBAM(z))) with z = relu(y·scale + shift) rebuilt from dec1's pre-BN conv output
+// in every pass.  CBAM's output feeds only the head's dot product and the head's input gradient is the
+// rank-1 dp[p]·w[c], so z, CBAM's output and that gradient are never stored.  The forward reads y twice
+// (F1 channel pooling; F2 per-pixel statistics, which also forms q[p] = Σ_c w·(z·att): q does not
+// depend on sa, so F3 is a per-pixel pass that reads no [M][C] tensor), the backward reads it once (B1,
+// the per-(sample, channel) sums) and writes dz once (B2).
+//
+// Every pass over y uses the row-slice shape of k_bn_relu_head_fwd_rows: block (TPP = C / 4, 256 / TPP),
+// a row's channel groups on adjacent lanes with one 16-byte (fp32) or 8-byte (bf16) load each, reduced
+// over the row with an xor butterfly.  A block's rows lie inside one sample (grid (slices, B)), so the
+// per-(sample, channel) vectors stay in registers.  Reductions over H·W are two-level with fp64
+// partials summed in a fixed order: no atomics, run-to-run deterministic.
+//
+// F3 takes sa[p] out of the channel sum: logit = sa·Σ_c w·(z·att) + bias, where the unfused composition
+// sums w·((z·att)·sa).  The two differ in fp32 rounding only.
+namespace {
+__device__ __forceinline__ float bn_relu1(float y, float s, float t) { return fmaxf(__fmaf_rn(y, s, t), 0.f); }
+
+template <bool YB, int TPP>
+__device__ __forceinline__ void cbh_z(const float* __restrict__ y, int64_t row, int c, const float4& s, const float4& t,
+                                      float (&z)[4]) {
+    const float4 v = load4<YB>(y, row * (4 * TPP) + c);
+    z[0] = bn_relu1(v.x, s.x, t.x);
+    z[1] = bn_relu1(v.y, s.y, t.y);
+    z[2] = bn_relu1(v.z, s.z, t.z);
+    z[3] = bn_relu1(v.w, s.w, t.w);
+}
+
+// F1: part[b][s][3][C] = {Σ z, max z, first argmax pixel} of slice s (k_chan_pool's layout; then
+// k_chan_pool_final)
+template <bool YB, int TPP>
+__global__ __launch_bounds__(256) void k_cbh_pool(const float* __restrict__ y, const float* __restrict__ scale,
+                                                  const float* __restrict__ shift, int64_t HW, int64_t rps,
+                                                  double* __restrict__ part) {
+    constexpr int C = 4 * TPP;
+    const int tx = threadIdx.x, ty = threadIdx.y, RY = blockDim.y, c = tx * 4;
+    const int S = gridDim.x, s = blockIdx.x, b = blockIdx.y;
+    const float4 sc = *reinterpret_cast<const float4*>(scale + c);
+    const float4 sh = *reinterpret_cast<const float4*>(shift + c);
+    const int64_t r0 = (int64_t)s * rps, r1 = min(HW, r0 + rps), base = (int64_t)b * HW;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int64_t mi[4] = {HW, HW, HW, HW};   // "none": loses every tie against a real index
+    // four rows per pass of the loop, their loads issued together (memory-level parallelism)
+    for (int64_t rb = r0 + ty; rb < r1; rb += 4 * RY) {
+        float z[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (rb + u * RY < r1) cbh_z<YB, TPP>(y, base + rb + u * RY, c, sc, sh, z[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t r = rb + u * RY;
+            if (r >= r1) break;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                sum[k] += z[u][k];
+                if (z[u][k] > mx[k]) { mx[k] = z[u][k]; mi[k] = r; }
+            }
+        }
+    }
+    __shared__ double red[256 * 12];   // [RY][TPP][4]{Σ, max, argmax}
+    double* mine = red + (ty * TPP + tx) * 12;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { mine[k * 3] = sum[k]; mine[k * 3 + 1] = mx[k]; mine[k * 3 + 2] = (double)mi[k]; }
+    __syncthreads();
+    for (int m = RY >> 1; m >= 1; m >>= 1) {   // fixed tree over the row lanes
+        if (ty < m) {
+            const double* o = red + ((ty + m) * TPP + tx) * 12;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float v = (float)mine[k * 3 + 1];
+                int64_t i = (int64_t)mine[k * 3 + 2];
+                amax_merge(v, i, (float)o[k * 3 + 1], (int64_t)o[k * 3 + 2]);
+                mine[k * 3] += o[k * 3];
+                mine[k * 3 + 1] = v;
+                mine[k * 3 + 2] = (double)i;
+            }
+        }
+        __syncthreads();
+    }
+    if (ty == 0) {
+        double* p = part + (((int64_t)b * S + s) * 3) * C + c;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { p[k] = mine[k * 3]; p[C + k] = mine[k * 3 + 1]; p[2 * C + k] = mine[k * 3 + 2]; }
+    }
+}
+
+// F2: per pixel s[p] = {mean_c z·att, max_c z·att}, sidx[p] = first argmax channel, q[p] = Σ_c w·(z·att)
+template <bool YB, int TPP>
+__global__ __launch_bounds__(256) void k_cbh_spool(Cbam A, const float* __restrict__ y, const float* __restrict__ scale,
+                                                   const float* __restrict__ shift, const float* __restrict__ w,
+                                                   float* __restrict__ q, int64_t HW, int64_t rps) {
+    constexpr int C = 4 * TPP;
+    const int tx = threadIdx.x, RY = blockDim.y, c = tx * 4, b = blockIdx.y;
+    const float4 sc = *reinterpret_cast<const float4*>(scale + c);
+    const float4 sh = *reinterpret_cast<const float4*>(shift + c);
+    const float4 wv = *reinterpret_cast<const float4*>(w + c);
+    const float4 at = *reinterpret_cast<const float4*>(A.att + (int64_t)b * C + c);
+    const int64_t r1 = min(HW, (int64_t)(blockIdx.x + 1) * rps), base = (int64_t)b * HW;
+    for (int64_t r = (int64_t)blockIdx.x * rps + threadIdx.y; r < r1; r += RY) {
+        float z[4];
+        cbh_z<YB, TPP>(y, base + r, c, sc, sh, z);
+        const float v0 = z[0] * at.x, v1 = z[1] * at.y, v2 = z[2] * at.z, v3 = z[3] * at.w;
+        float sum = (v0 + v1) + (v2 + v3);
+        float qq = (wv.x * v0 + wv.y * v1) + (wv.z * v2 + wv.w * v3);
+        float mx = v0;
+        int mi = c;
+        if (v1 > mx) { mx = v1; mi = c + 1; }
+        if (v2 > mx) { mx = v2; mi = c + 2; }
+        if (v3 > mx) { mx = v3; mi = c + 3; }
+        // (a row's TPP lanes share r: all of them are in the loop together)
+#pragma unroll
+        for (int o = TPP / 2; o > 0; o >>= 1) {
+            sum += __shfl_xor(sum, o);
+            qq += __shfl_xor(qq, o);
+            const float ov = __shfl_xor(mx, o);
+            const int oi = __shfl_xor(mi, o);
+            if (ov > mx || (ov == mx && oi < mi)) { mx = ov; mi = oi; }
+        }
+        if (tx == 0) {
+            const int64_t p = base + r;
+            *reinterpret_cast<float2*>(A.s + p * 2) = make_float2(sum / (float)C, mx);
+            A.sidx[p] = mi;
+            q[p] = qq;
+        }
+    }
+}
+
+// F3: logit = sa·q + bias (per-pixel data only)
+__global__ void k_cbh_head(Cbam A, CbamHead Hd, float* __restrict__ pred, int64_t M) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= M) return;
+    const float z = A.sa[p] * Hd.q[p] + Hd.b[0];
+    const float sg = 1.f / (1.f + expf(-z));
+    Hd.sig[p] = sg;
+    pred[p] = sg * Hd.md;
+}
+
+// dp = dpred·md·σ'(logit); the spatial conv's logit gradient dlog = dp·q·σ'(sa)
+__global__ void k_cbh_dlog(Cbam A, CbamHead Hd, const float* __restrict__ dpred, int64_t M) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= M) return;
+    const float sg = Hd.sig[p], s = A.sa[p];
+    const float dp = dpred[p] * Hd.md * ((1.f - sg) * sg);
+    Hd.dp[p] = dp;
+    A.dlog[p] = (dp * Hd.q[p]) * (1.f - s) * s;
+}
+
+// B1: part[b][s][2C + 1] = {Hs[c] = Σ dp·sa·z, R[c] = Σ (ds0/C + [c == sidx]·ds1)·z, Σ dp} of slice s
+template <bool YB, int TPP>
+__global__ __launch_bounds__(256) void k_cbh_sums(Cbam A, const float* __restrict__ y, const float* __restrict__ scale,
+                                                  const float* __restrict__ shift, const float* __restrict__ dp,
+                                                  int64_t HW, int64_t rps, double* __restrict__ part) {
+    constexpr int C = 4 * TPP;
+    const int tx = threadIdx.x, ty = threadIdx.y, RY = blockDim.y, c = tx * 4;
+    const int S = gridDim.x, s = blockIdx.x, b = blockIdx.y;
+    const float4 sc = *reinterpret_cast<const float4*>(scale + c);
+    const float4 sh = *reinterpret_cast<const float4*>(shift + c);
+    const int64_t r0 = (int64_t)s * rps, r1 = min(HW, r0 + rps), base = (int64_t)b * HW;
+    double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // Hs[4], R[4], Σ dp
+    for (int64_t rb = r0 + ty; rb < r1; rb += 4 * RY) {
+        float z[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (rb + u * RY < r1) cbh_z<YB, TPP>(y, base + rb + u * RY, c, sc, sh, z[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t r = rb + u * RY;
+            if (r >= r1) break;
+            const int64_t p = base + r;
+            const float d = dp[p], hs = d * A.sa[p];
+            const float2 ds = *reinterpret_cast<const float2*>(A.ds + p * 2);
+            const float d0 = ds.x / (float)C;
+            const int si = A.sidx[p] - c;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc[k] += (double)(hs * z[u][k]);
+                acc[4 + k] += (double)((si == k ? d0 + ds.y : d0) * z[u][k]);
+            }
+            acc[8] += d;
+        }
+    }
+    __shared__ double red[256 * 9];
+    double* mine = red + (ty * TPP + tx) * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) mine[k] = acc[k];
+    __syncthreads();
+    for (int m = RY >> 1; m >= 1; m >>= 1) {   // fixed tree over the row lanes
+        if (ty < m) {
+            const double* o = red + ((ty + m) * TPP + tx) * 9;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) mine[k] += o[k];
+        }
+        __syncthreads();
+    }
+    if (ty == 0) {
+        double* p = part + ((int64_t)b * S + s) * (2 * C + 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { p[c + k] = mine[k]; p[C + c + k] = mine[4 + k]; }
+        if (tx == 0) p[2 * C] = mine[8];
+    }
+}
+// per sample, the slices summed in order: hs[b][c] = Hs, datt[b][c] = w[c]·Hs + R, dbp[b] = Σ dp
+__global__ void k_cbh_final1(Cbam A, const float* __restrict__ w, const double* __restrict__ part, int S,
+                             double* __restrict__ hs, double* __restrict__ datt, double* __restrict__ dbp) {
+    const int b = blockIdx.x, C = A.C;
+    for (int c = threadIdx.x; c <= C; c += blockDim.x) {
+        if (c == C) {
+            double d = 0.0;
+            for (int s = 0; s < S; ++s) d += part[((int64_t)b * S + s) * (2 * C + 1) + 2 * C];
+            dbp[b] = d;
+            continue;
+        }
+        double h = 0.0, r = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double* p = part + ((int64_t)b * S + s) * (2 * C + 1);
+            h += p[c];
+            r += p[C + c];
+        }
+        hs[(int64_t)b * C + c] = h;
+        datt[(int64_t)b * C + c] = (double)w[c] * h + r;
+    }
+}
+// d out_conv.weight[c] = Σ_b att[b][c]·Hs[b][c], d out_conv.bias = Σ_b dbp[b]
+__global__ void k_cbh_final2(Cbam A, CbamHead Hd, const double* __restrict__ hs, const double* __restrict__ dbp,
+                             int B) {
+    const int C = A.C;
+    for (int c = threadIdx.x; c <= C; c += blockDim.x) {
+        double acc = 0.0;
+        if (c == C) {
+            for (int b = 0; b < B; ++b) acc += dbp[b];
+            Hd.gb[0] = (float)acc;
+        } else {
+            for (int b = 0; b < B; ++b) acc += (double)A.att[(int64_t)b * C + c] * hs[(int64_t)b * C + c];
+            Hd.gw[c] = (float)acc;
+        }
+    }
+}
+
+// B2: dz = (dp·w·sa + ds0/C + [c == sidx]·ds1)·att + dva/HW + [p == amax]·dvm  (k_head_da's g = dp·w
+// put through cbam_dx1 / k_cbam_dx); reads per-pixel and per-(sample, channel) data only
+template <int TPP>
+__global__ __launch_bounds__(256) void k_cbh_dz(Cbam A, const float* __restrict__ w, const float* __restrict__ dp,
+                                                int64_t HW, int64_t rps, float* __restrict__ dz) {
+    constexpr int C = 4 * TPP;
+    const int tx = threadIdx.x, RY = blockDim.y, c = tx * 4, b = blockIdx.y;
+    const int64_t bc = (int64_t)b * C + c;
+    const float4 wv = *reinterpret_cast<const float4*>(w + c);
+    const float4 at = *reinterpret_cast<const float4*>(A.att + bc);
+    const float4 va = *reinterpret_cast<const float4*>(A.dva + bc);
+    const float4 vm = *reinterpret_cast<const float4*>(A.dvm + bc);
+    const int4 am = *reinterpret_cast<const int4*>(A.amax + bc);
+    const float inv = 1.0f / (float)HW;
+    const float wk[4] = {wv.x, wv.y, wv.z, wv.w}, ak[4] = {at.x, at.y, at.z, at.w};
+    const float vak[4] = {va.x * inv, va.y * inv, va.z * inv, va.w * inv}, vmk[4] = {vm.x, vm.y, vm.z, vm.w};
+    const int amk[4] = {am.x, am.y, am.z, am.w};
+    const int64_t r1 = min(HW, (int64_t)(blockIdx.x + 1) * rps), base = (int64_t)b * HW;
+    for (int64_t r = (int64_t)blockIdx.x * rps + threadIdx.y; r < r1; r += RY) {
+        const int64_t p = base + r;
+        const float d = dp[p], sa = A.sa[p];
+        const float2 ds = *reinterpret_cast<const float2*>(A.ds + p * 2);
+        const float d0 = ds.x / (float)C;
+        const int si = A.sidx[p] - c;
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float dx1 = (d * wk[k]) * sa + d0;
+            if (si == k) dx1 += ds.y;
+            o[k] = dx1 * ak[k] + vak[k];
+            if ((int64_t)amk[k] == r) o[k] += vmk[k];
+        }
+        *reinterpret_cast<float4*>(dz + p * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// f(integral_constant<int, C / 4>): the kernel instances are picked at compile time
+template <class F>
+void cbh_tpp(int C, F&& f) {
+    switch (C / 4) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 16: f(std::integral_constant<int, 16>{}); break;
+        default: f(std::integral_constant<int, 32>{}); break;
+    }
+}
+struct CbhGrid {
+    int TPP, RY, S;   // block (TPP, RY), S row slices per sample
+    int64_t rps;
+};
+// per-pixel passes: slices of about 16 rows per row lane
+inline CbhGrid cbh_rows(int64_t HW, int C) {
+    CbhGrid g;
+    g.TPP = C / 4;
+    g.RY = 256 / g.TPP;
+    g.S = (int)std::max<int64_t>(1, std::min<int64_t>(65535, cdiv(HW, (int64_t)g.RY * 16)));
+    g.rps = (HW + g.S - 1) / g.S;
+    return g;
+}
+// per-(sample, channel) reductions: chan_pool's slice count
+inline CbhGrid cbh_slices(int64_t HW, int C) {
+    CbhGrid g = cbh_rows(HW, C);
+    g.S = chan_pool_slices(HW);
+    g.rps = (HW + g.S - 1) / g.S;
+    return g;
+}
+void cbh_check(const Cbam& A, int B) {
+    const int c4 = A.C / 4;
+    if (A.C % 4 || c4 < 1 || c4 > 32 || (c4 & (c4 - 1)) || B < 1 || B > 65535)
+        throw std::runtime_error("cbam_head: C / 4 must be a power of two <= 32 (head_fusable), B <= 65535");
+}
+}  // namespace
+
+int64_t cbam_head_scratch_doubles(int B, int64_t HW, int C) {
+    // B1's partials [B][S][2C + 1], then hs and datt [B][C] each and dbp [B]; or the CBAM kernels' own
+    const int S = chan_pool_slices(HW);
+    return std::max<int64_t>(attn_scratch_doubles(B, HW, C), (int64_t)B * S * (2 * C + 1) + (int64_t)B * (2 * C + 1) + 64);
+}
+
+void cbam_head_fwd(const Cbam& A, const CbamHead& Hd, int B, int H, int W, float* pred, double* scratch,
+                   hipStream_t st) {
+    cbh_check(A, B);
+    const int C = A.C;
+    const int64_t HW = (int64_t)H * W, M = (int64_t)B * HW;
+    CAD_NO_ALIAS("cbam_head_fwd",
+                 {aview(pred, M, 1, 0, 1, 4, "pred"), aview(Hd.q, M, 1, 0, 1, 4, "q"), aview(Hd.sig, M, 1, 0, 1, 4, "sig"),
+                  aview(A.s, M, 2, 0, 2, 4, "s"), aview(A.sidx, M, 1, 0, 1, 4, "sidx"), aview(A.sa, M, 1, 0, 1, 4, "sa"),
+                  aview(A.att, B, C, 0, C, 4, "att"), aview(A.avg, B, C, 0, C, 4, "avg"), aview(A.mx, B, C, 0, C, 4, "max"),
+                  aview(A.amax, B, C, 0, C, 4, "amax")},
+                 {aview(Hd.y, M, C, 0, C, Hd.y_bf16 ? 2 : 4, "y"), aview(Hd.scale, 1, C, 0, C, 4, "scale"),
+                  aview(Hd.shift, 1, C, 0, C, 4, "shift"), aview(Hd.w, 1, C, 0, C, 4, "head weight")});
+    const CbhGrid gs = cbh_slices(HW, C), gr = cbh_rows(HW, C);
+    cbh_tpp(C, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        auto kern = Hd.y_bf16 ? k_cbh_pool<true, T> : k_cbh_pool<false, T>;
+        hipLaunchKernelGGL(kern, dim3(gs.S, B), dim3(gs.TPP, gs.RY), 0,
+                           st, Hd.y, Hd.scale, Hd.shift, HW, gs.rps, scratch);
+    });
+    hipLaunchKernelGGL(k_chan_pool_final, dim3(cdiv((int64_t)B * C, 256)), dim3(256), 0, st, scratch, gs.S, C, B, HW,
+                       A.avg, A.mx, A.amax);
+    hipLaunchKernelGGL(k_cbam_mlp_fwd, dim3(B), dim3(256), 0, st, A);
+    cbh_tpp(C, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        auto kern = Hd.y_bf16 ? k_cbh_spool<true, T> : k_cbh_spool<false, T>;
+        hipLaunchKernelGGL(kern, dim3(gr.S, B), dim3(gr.TPP, gr.RY),
+                           0, st, A, Hd.y, Hd.scale, Hd.shift, Hd.w, Hd.q, HW, gr.rps);
+    });
+    hipLaunchKernelGGL(k_cbam_sconv, dim3(cdiv(M, 256)), dim3(256), 0, st, A, H, W, M);
+    hipLaunchKernelGGL(k_cbh_head, dim3(cdiv(M, 256)), dim3(256), 0, st, A, Hd, pred, M);
+}
+
+void cbam_head_bwd(const Cbam& A, const CbamHead& Hd, const float* dpred, int B, int H, int W, float* dz,
+                   double* scratch, hipStream_t st) {
+    cbh_check(A, B);
+    const int C = A.C;
+    const int64_t HW = (int64_t)H * W, M = (int64_t)B * HW;
+    CAD_NO_ALIAS("cbam_head_bwd",
+                 {aview(dz, M, C, 0, C, 4, "dz"), aview(Hd.dp, M, 1, 0, 1, 4, "dp"), aview(A.dlog, M, 1, 0, 1, 4, "dlog"),
+                  aview(A.ds, M, 2, 0, 2, 4, "ds"), aview(Hd.gw, 1, C, 0, C, 4, "head weight grad"),
+                  aview(Hd.gb, 1, 1, 0, 1, 4, "head bias grad"), aview(A.gw1, A.Cr, C, 0, C, 4, "fc1 grad"),
+                  aview(A.gw2, C, A.Cr, 0, A.Cr, 4, "fc2 grad"), aview(A.gwsp, 1, 98, 0, 98, 4, "spatial conv grad")},
+                 {aview(Hd.y, M, C, 0, C, Hd.y_bf16 ? 2 : 4, "y"), aview(dpred, M, 1, 0, 1, 4, "dpred"),
+                  aview(Hd.sig, M, 1, 0, 1, 4, "sig"), aview(Hd.q, M, 1, 0, 1, 4, "q"), aview(A.sa, M, 1, 0, 1, 4, "sa"),
+                  aview(A.s, M, 2, 0, 2, 4, "s"), aview(A.sidx, M, 1, 0, 1, 4, "sidx"), aview(A.att, B, C, 0, C, 4, "att"),
+                  aview(Hd.w, 1, C, 0, C, 4, "head weight")});
+    hipLaunchKernelGGL(k_cbh_dlog, dim3(cdiv(M, 256)), dim3(256), 0, st, A, Hd, dpred, M);
+    hipLaunchKernelGGL(k_cbam_sconv_bwd_in, dim3(cdiv(M, 256)), dim3(256), 0, st, A, H, W, M);
+    const int SW = (int)std::max<int64_t>(1, std::min<int64_t>(256, M / 4096));
+    hipLaunchKernelGGL(k_cbam_sconv_wgrad, dim3(98, SW), dim3(256), 0, st, A, H, W, M, (M + SW - 1) / SW, scratch);
+    hipLaunchKernelGGL(k_cbam_sconv_wgrad_final, dim3(1), dim3(128), 0, st, A, scratch, SW);
+    const CbhGrid gs = cbh_slices(HW, C), gr = cbh_rows(HW, C);
+    double* hs = scratch + (int64_t)B * gs.S * (2 * C + 1);
+    double* datt = hs + (int64_t)B * C;
+    double* dbp = datt + (int64_t)B * C;
+    cbh_tpp(C, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        auto kern = Hd.y_bf16 ? k_cbh_sums<true, T> : k_cbh_sums<false, T>;
+        hipLaunchKernelGGL(kern, dim3(gs.S, B), dim3(gs.TPP, gs.RY), 0,
+                           st, A, Hd.y, Hd.scale, Hd.shift, Hd.dp, HW, gs.rps, scratch);
+    });
+    hipLaunchKernelGGL(k_cbh_final1, dim3(B), dim3(128), 0, st, A, Hd.w, scratch, gs.S, hs, datt, dbp);
+    hipLaunchKernelGGL(k_cbh_final2, dim3(1), dim3(128), 0, st, A, Hd, hs, dbp, B);
+    hipLaunchKernelGGL(k_cbam_mlp_bwd, dim3(B), dim3(256), 0, st, A, datt, 1);
+    const int64_t nw = 2 * (int64_t)C * A.Cr + C + A.Cr;
+    hipLaunchKernelGGL(k_cbam_mlp_wgrad, dim3(cdiv(nw, 256)), dim3(256), 0, st, A, B);
+    cbh_tpp(C, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_cbh_dz<T>, dim3(gr.S, B), dim3(gr.TPP, gr.RY), 0, st, A, Hd.w, Hd.dp, HW, gr.rps, dz);
+    });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -482,6 +482,27 @@ void cbam_fwd(const Cbam& A, const float* x, int B, int H, int W, float* out, in
 void cbam_bwd(const Cbam& A, const float* x, const float* g, int64_t ldg, int gcoff, int B, int H, int W, float* dx,
               double* scratch, hipStream_t st);
 
+// Level-0 attention head of IntrinsicsAttentionUNetImpl (intrinsics_unet.h:361-366), fused:
+//   pred = md * sigmoid(out_conv(CBAM(relu(y * scale + shift))))
+// with z = relu(bn2(y)) rebuilt from dec1's pre-BN conv output in every pass: neither z, nor CBAM's
+// output, nor the head's input gradient is ever stored (attn_kernels.hip).  C must be head_fusable.
+struct CbamHead {
+    const float* y = nullptr;   // [M][C] pre-BN conv2 output, fp32 or bf16 (y_bf16)
+    bool y_bf16 = false;
+    const float *scale = nullptr, *shift = nullptr;   // bn2 coefficients [C]
+    const float *w = nullptr, *b = nullptr;           // out_conv.weight [C], out_conv.bias [1]
+    float md = 0.f;
+    float *q = nullptr, *sig = nullptr, *dp = nullptr;   // [M]: Σ_c w·z·att, sigmoid, dL/dlogit
+    float *gw = nullptr, *gb = nullptr;               // out_conv gradients
+};
+int64_t cbam_head_scratch_doubles(int B, int64_t HW, int C);
+// writes pred [M] and the state the backward needs (A.avg .. A.sa, Hd.q, Hd.sig)
+void cbam_head_fwd(const Cbam& A, const CbamHead& Hd, int B, int H, int W, float* pred, double* scratch,
+                   hipStream_t st);
+// dz (dense [M][C], fp32) = dL/dz given dpred [M]; writes the CBAM and out_conv gradients
+void cbam_head_bwd(const Cbam& A, const CbamHead& Hd, const float* dpred, int B, int H, int W, float* dz,
+                   double* scratch, hipStream_t st);
+
 // One PerspectiveCorrectionLayerImpl (pcl_layer.h:29-181, hidden 128)
 constexpr int kPclHidden = 128;
 struct Pcl {

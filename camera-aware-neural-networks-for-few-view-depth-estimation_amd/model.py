@@ -5,6 +5,7 @@ the reference's own code:
 
   BaselineUNet            BaselineUNetImpl           src/models/baseline_unet.h:122-208
   IntrinsicsConditionedUNet IntrinsicsConditionedUNetImpl src/models/intrinsics_unet.h:137-270
+  IntrinsicsAttentionUNet IntrinsicsAttentionUNetImpl src/models/intrinsics_unet.h:278-385
   RayConditionedUNet      config-3 composite: enc1 = RayEnhancedConv (geometry_aware_network.h:17-65),
                           FiLM blocks after (intrinsics_unet.h:16-113)
   CombinedDepthLoss       CombinedDepthLoss          src/loss/depth_loss.h:366-479
@@ -37,7 +38,7 @@ def _ptr(t: torch.Tensor):
     return C.c_void_p(t.data_ptr())
 
 
-MODEL_BASELINE, MODEL_INTRINSICS_FILM, MODEL_RAY_FILM = 0, 1, 2   # CAD_MODEL_* of cad.h
+MODEL_BASELINE, MODEL_INTRINSICS_FILM, MODEL_RAY_FILM, MODEL_INTRINSICS_ATTN = 0, 1, 2, 3   # CAD_MODEL_* of cad.h
 
 
 def _histograms(model, fn, which):
@@ -247,6 +248,38 @@ class IntrinsicsConditionedUNet(BaselineUNet):
 
     def forward(self, x, intrinsics, out=None):   # noqa: D401 (reference signature)
         return self.forward_cam(x, intrinsics, out)
+
+
+class IntrinsicsAttentionUNet(IntrinsicsConditionedUNet):
+    """IntrinsicsAttentionUNetImpl(in_channels, init_features, camera_dim=4, max_depth) on MI355X: the FiLM
+    U-Net with a CBAM (att4 .. att1, spatial_attention.h:142-191) after every decoder block, ahead of the
+    1x1 depth head (intrinsics_unet.h:278-385).  Level 0 runs as the fused attention head when
+    init_features / 4 is a power of two <= 32."""
+
+    MODEL = MODEL_INTRINSICS_ATTN
+
+    def _int_buffer(self, name):
+        return self.debug_buffer(name).view(torch.int32)
+
+    def attention_maps(self, level):
+        """CBAMImpl::getAttentionMaps of att<level> (1..4) for the last forward:
+        (channel_att [B, C], spatial_att [B, 1, H_l, W_l]) as host tensors."""
+        if level not in (1, 2, 3, 4):
+            raise ValueError(f"level must be 1..4 (att1 .. att4), not {level!r}")
+        l = level - 1
+        C_l = self.init_features << l
+        att = self.debug_buffer(f"att{l}").view(-1, C_l)
+        sa = self.debug_buffer(f"sa{l}").view(att.shape[0], 1, self.height >> l, self.width >> l)
+        return att, sa
+
+    def attention_decisions(self, level):
+        """The two argmax decisions of att<level>'s last forward: (argmax pixel of the channel max-pool
+        [B, C], argmax channel of the spatial max [B, H_l, W_l]), int64 host tensors."""
+        l = level - 1
+        C_l = self.init_features << l
+        amax = self._int_buffer(f"amax{l}").view(-1, C_l).long()
+        sidx = self._int_buffer(f"sidx{l}").view(amax.shape[0], self.height >> l, self.width >> l).long()
+        return amax, sidx
 
 
 class RayConditionedUNet(IntrinsicsConditionedUNet):

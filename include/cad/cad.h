@@ -99,6 +99,11 @@ typedef struct cad_adam cad_adam;
 #define CAD_MODEL_BASELINE 0        /* BaselineUNetImpl */
 #define CAD_MODEL_INTRINSICS_FILM 1 /* IntrinsicsConditionedUNetImpl (camera_dim 4) */
 #define CAD_MODEL_RAY_FILM 2        /* enc1 = RayEnhancedConv(3, f, 4, use_rays), FiLM blocks after */
+/* IntrinsicsAttentionUNetImpl (intrinsics_unet.h:278-385): INTRINSICS_FILM with a CBAM (att4 .. att1,
+ * spatial_attention.h:142-191) after every decoder block.  named_parameters() keeps the reference's
+ * registration order (att4.* .. att1.* between dec1.* and out_conv.*); in the flat slab att<k> follows
+ * dec<k>, so each backward stage's gradient range stays contiguous (stage k = dec<k> + att<k>) */
+#define CAD_MODEL_INTRINSICS_ATTN 3
 
 typedef struct {
     int in_channels;   /* 3 */
@@ -515,6 +520,9 @@ int cad_loader_next(cad_loader* L, float* rgb, float* depth, float* K, void* str
 /* ---- debugging: synchronous host copy of an internal NHWC activation buffer by name
  * ("x0", "cat<l>", "dcat<l>", "pool<l>", "dout<l>", "bott", "Sa", "Sb", "Sc",
  *  "enc<l>.y1|a1|y2", "dec<l>.y1|a1|y2"); numel = rows*channels of the last forward's batch.
+ * CAD_MODEL_INTRINSICS_ATTN adds the CBAM state of att<l+1>: "att<l>" [B][C] channel attention, "sa<l>"
+ * [B*H_l*W_l] spatial attention, and the two argmax decisions "amax<l>" [B][C] (pixel within the sample) and
+ * "sidx<l>" [B*H_l*W_l] (channel), int32 bit-copied into the float buffer.
  * Returns the element count (host may be NULL to query), or -1 for an unknown name — and, on the
  * bf16 engine (pre-split operands), for the buffers whose fp32 copy that path does not write
  * ("Sb", "bott", "pool<l>", "dout1..3", every block's a1); cad_last_error() says which. */
@@ -703,6 +711,19 @@ cad_status cad_op_cbam(const float* x, const float* g, const float* params, int 
                        float* dx, float* grads, void* stream);
 cad_status cad_op_pcl(const float* u, const float* camn, const float* g, const float* params, int B, int H, int W,
                       int C, float* out, float* du, float* grads, float* theta, void* stream);
+/* level 0 of CAD_MODEL_INTRINSICS_ATTN, forward + backward, on device tensors (tests and A/B timing; state
+ * allocated per call):  z = relu(y * scale + shift),  pred = max_depth * sigmoid(head_w . CBAM(z) + head_b).
+ * y [B*H*W][C] fp32, or bf16 values when y_bf16; scale / shift [C]; cbam_params / cbam_grads packed as
+ * cad_op_cbam's; head_w [C], head_b [1]; head_grads [C + 1] = {d head_w, d head_b}; dpred, pred [B*H*W];
+ * dz [B*H*W][C] = dL/dz (not yet masked by the ReLU).  fused = 1: the fused attention head (C / 4 a power
+ * of two <= 32), which stores neither z nor CBAM's output; fused = 0: bn_relu_fwd, cbam_fwd, head_fwd,
+ * head_bwd, cbam_bwd.  sidx_out [B*H*W] / amax_out [B*C] (nullable, device int32): CBAM's two argmax
+ * decisions.  elapsed_ms (nullable, host): the forward + backward is run a second time between two device
+ * events and their distance stored (the first run warms up) */
+cad_status cad_op_cbam_head(const float* y, int y_bf16, const float* scale, const float* shift, const float* cbam_params,
+                            const float* head_w, const float* head_b, float max_depth, const float* dpred, int B, int H,
+                            int W, int C, int fused, float* pred, float* dz, float* cbam_grads, float* head_grads,
+                            int* sidx_out, int* amax_out, float* elapsed_ms, void* stream);
 /* test hook: buffer of the last step ("cat<l>", "dcat<l>", "x<l>", "u<l>", "z<l>"; NHWC rows) -> host;
  * returns the element count (host NULL: count only) or -1 */
 int64_t cad_geonet_debug_buffer(cad_geonet* h, const char* name, float* host, int64_t numel);

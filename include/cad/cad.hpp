@@ -11,6 +11,7 @@
 #ifndef CAD_CAD_HPP
 #define CAD_CAD_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <map>
@@ -218,6 +219,48 @@ public:
     }
     DeviceTensor operator()(const DeviceTensor& x, const DeviceTensor& intrinsics) { return forward(x, intrinsics); }
 };
+
+// IntrinsicsAttentionUNetImpl(in, f, camera_dim = 4, max_depth)   (intrinsics_unet.h:278-385): the FiLM
+// U-Net with a CBAM (att4 .. att1) after every decoder block, ahead of the 1x1 depth head; same
+// forward(x, camera_intrinsics (B,4)).  Works with TensorBoardTrainerEnhanced, ModelEvaluator, Predictor
+// and save / load like IntrinsicsConditionedUNetImpl.
+class IntrinsicsAttentionUNetImpl : public IntrinsicsConditionedUNetImpl {
+public:
+    explicit IntrinsicsAttentionUNetImpl(int in_channels = 3, int init_features = 64, int camera_dim = 4,
+                                         float max_depth_value = 10.0f, cad::Workspace ws = {})
+        : IntrinsicsConditionedUNetImpl(in_channels, init_features, camera_dim, max_depth_value, ws,
+                                        CAD_MODEL_INTRINSICS_ATTN) {}
+};
+
+// intrinsics_unet and intrinsics_attention_unet differ only by the att<k>.* tensors.  A checkpoint's
+// tensor names say which one wrote it: the message for a model of the other kind, naming both parameter
+// counts and the model.architecture value that loads the file ("" when the two agree)
+inline std::string attention_checkpoint_mismatch(const BaselineUNetImpl& m, bool ckpt_has_attention,
+                                                 const std::string& path) {
+    const int kind = cad_unet_model(m.handle());
+    if (kind != CAD_MODEL_INTRINSICS_FILM && kind != CAD_MODEL_INTRINSICS_ATTN) return "";
+    const bool attn = kind == CAD_MODEL_INTRINSICS_ATTN;
+    if (attn == ckpt_has_attention) return "";
+    int64_t att = 0;
+    const char* name;
+    int nd;
+    int64_t shp[4];
+    cad::check(cad_unet_tensor_info(m.handle(), 0, 0, &name, &nd, shp), "tensor_info");   // enc1.conv1.weight: f
+    for (int64_t l = 0, C = shp[0]; l < 4; ++l, C *= 2) {
+        const int64_t Cr = std::max<int64_t>(1, C / 16);
+        att += 2 * C * Cr + C + Cr + 98;
+    }
+    const int64_t mine = m.count_parameters(), other = attn ? mine - att : mine + att;
+    const std::string a = "intrinsics_attention_unet", f = "intrinsics_unet";
+    return "checkpoint '" + path + "' holds " + (ckpt_has_attention ? a : f) + " (" + std::to_string(other) +
+           " parameters), this model is " + (attn ? a : f) + " (" + std::to_string(mine) +
+           " parameters): set model.architecture: " + (ckpt_has_attention ? a : f) + " to load it";
+}
+inline bool has_attention_tensors(const std::vector<NamedTensor>& ts) {
+    for (const auto& t : ts)
+        if (t.name == "att1.spatial_attention.conv.weight") return true;
+    return false;
+}
 
 // Config-3 composite: enc1 = RayEnhancedConv(3, f, 4, use_rays) fed cat(x, rays(K)) (geometry_aware_network.h:17-65),
 // FiLM blocks after; same forward(x, intrinsics) (rays derived on device from the intrinsics).

@@ -17,6 +17,7 @@
 #include <functional>
 #include <iomanip>
 #include <sstream>
+#include <type_traits>
 
 #include "cad.hpp"
 #include "trainer.hpp"
@@ -224,6 +225,12 @@ inline void load_model_state(const std::string& path, Model& m) {
         if (!f || cnt < 0 || cnt > (int64_t(1) << 32)) throw std::runtime_error("corrupt checkpoint: " + path);
         t.value.resize((size_t)cnt);
         f.read((char*)t.value.data(), 4 * cnt);
+    }
+    if constexpr (std::is_base_of<BaselineUNetImpl, Model>::value) {
+        if (f) {
+            const std::string why = attention_checkpoint_mismatch(m, has_attention_tensors(ts), path);
+            if (!why.empty()) throw std::runtime_error(why);
+        }
     }
     if (!f || m.load(ts) != n) throw std::runtime_error("checkpoint does not match the model: " + path);
 }

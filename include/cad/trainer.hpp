@@ -342,6 +342,10 @@ inline void load_training_state(const std::string& path, BaselineUNetImpl& m, op
         t.value.resize((size_t)cnt);
         f.read((char*)t.value.data(), 4 * cnt);
     }
+    if (f) {
+        const std::string why = attention_checkpoint_mismatch(m, has_attention_tensors(ts), path);
+        if (!why.empty()) throw std::runtime_error(why);
+    }
     if (!f || m.load(ts) != n) throw std::runtime_error("checkpoint does not match the model: " + path);
     char tag[4];
     if (f.read(tag, 4) && std::memcmp(tag, "ADAM", 4) == 0) {
