@@ -16,9 +16,12 @@ def __getattr__(name):
     if name in ("BaselineUNet", "IntrinsicsConditionedUNet", "IntrinsicsAttentionUNet", "RayConditionedUNet", "CombinedDepthLoss", "Adam",
                 "Trainer", "Communicator", "save", "load", "clip_grad_norm_", "depth_metrics", "ray_directions", "camera_from_K",
                 "ResNetUNet", "GeometryAwareNetwork", "LightweightGeometryNetwork", "depth_metrics_full", "Evaluator",
-                "evaluate", "EVAL_KEYS", "valid_medians"):
+                "evaluate", "EVAL_KEYS", "valid_medians", "Optimizer"):
         from . import model
         return getattr(model, name)
+    if name == "lr_at":
+        from . import recipe
+        return recipe.lr_at
     if name in ("BatchAssembler", "AugSampler", "SunRGBDDataset", "PrefetchLoader"):
         from . import batch
         return getattr(batch, name)

@@ -41,6 +41,21 @@ class AdamOpts(C.Structure):
     _fields_ = [("lr", F), ("beta1", F), ("beta2", F), ("eps", F), ("weight_decay", F)]
 
 
+OPTIM_RULES = {"adam": 0, "adamw": 1, "sgd": 2}   # CAD_OPTIM_*
+
+
+class OptimOpts(C.Structure):
+    """cad_optim_opts (cad.h)."""
+    _fields_ = [("rule", I), ("lr", F), ("beta1", F), ("beta2", F), ("eps", F), ("weight_decay", F), ("momentum", F),
+                ("ema_decay", F)]
+
+
+class LrOpts(C.Structure):
+    """cad_lr_opts (cad.h)."""
+    _fields_ = [("lr", F), ("scheduler", C.c_char_p), ("step_size", I), ("gamma", F), ("warmup_epochs", I),
+                ("lr_min", F)]
+
+
 class CommStats(C.Structure):
     """cad_comm_stats (cad.h): exchange accounting of the overlapped backward all-reduce."""
     _fields_ = [("calls", I64), ("timed_calls", I64), ("buckets", I64), ("bytes", I64), ("exposed_ms", C.c_double),
@@ -188,6 +203,20 @@ SIGNATURES = {
     "cad_adam_step": (I, [P, P]),
     "cad_adam_set_lr": (I, [P, F]),
     "cad_adam_step_count": (I64, [P]),
+    "cad_optim_create": (I, [P, C.POINTER(OptimOpts), C.POINTER(P)]),
+    "cad_optim_destroy": (None, [P]),
+    "cad_optim_step": (I, [P, P]),
+    "cad_optim_set_lr": (I, [P, F]),
+    "cad_optim_lr": (F, [P]),
+    "cad_optim_rule": (I, [P]),
+    "cad_optim_step_count": (I64, [P]),
+    "cad_optim_set_step_count": (I, [P, I64]),
+    "cad_optim_state": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
+    "cad_optim_attach_ema": (I, [P, F, P]),
+    "cad_optim_ema_swap": (I, [P, P]),
+    "cad_optim_swapped": (I, [P]),
+    "cad_geonet_optim_step": (I, [P, C.POINTER(OptimOpts), P]),
+    "cad_lr_at": (I, [C.POINTER(LrOpts), I, I, FP]),
     "cad_loss_create": (I, [F, F, F, F, I, I, I, I, C.POINTER(P)]),
     "cad_loss_destroy": (None, [P]),
     "cad_loss_forward_backward": (I, [P, P, P, P, P, I, P, P, P]),

@@ -18,7 +18,11 @@
 // model.architecture selects the FiLM models and the geometry-aware networks (model.variant,
 // use_pcl, use_attention; single process) — the reference always builds BaselineUNet;
 // data.dataset_name "synthetic" trains on generated samples, anything else on the manifest's PNG / PNM /
-// JPEG files (csrc/host/jpeg.cpp decodes as cv::imread does); hardware.distributed runs DP over RCCL.
+// JPEG files (csrc/host/jpeg.cpp decodes as cv::imread does); hardware.distributed runs DP over RCCL;
+// optimization.recipe: declared (or --recipe declared) honours the recipe the config declares — optimizer
+// adam / adamw / sgd, lr_scheduler none / step / cosine with warmup, early_stopping, checkpointing.keep_last_n /
+// save_best_only, validation.primary_metric and an EMA of the weights (ema: {enabled, decay}) — where the
+// default, reference, trains Adam at a constant rate as the reference's running trainer does.
 #include <signal.h>
 #include <spawn.h>
 #include <sys/wait.h>
@@ -54,6 +58,7 @@ struct Args {
     int gpu = 0;
     bool debug = false, tensorboard = true;
     bool dry_run = false;   // print the (per-rank) run plan and exit before any GPU call
+    std::string recipe;     // --recipe reference|declared ("" = the config's optimization.recipe)
     std::vector<std::string> argv;
 };
 
@@ -69,6 +74,9 @@ void usage() {
                  "                        logging.tensorboard.tensorboard_dir/<experiment> and the scalars CSV in\n"
                  "                        the log directory (default: true; false writes neither)\n"
                  "      --dry-run         Print the run plan (per data-parallel rank) and exit; no GPU use\n"
+                 "      --recipe arg      reference: Adam at a constant rate, whatever the config declares (default);\n"
+                 "                        declared: honour optimization.optimizer / lr_scheduler / warmup, early_stopping,\n"
+                 "                        checkpointing.keep_last_n / save_best_only and ema (overrides optimization.recipe)\n"
                  "  -h, --help            Print help\n";
 }
 
@@ -91,6 +99,11 @@ Args parse_args(int argc, char** argv) {
         else if (k == "-g" || k == "--gpu") a.gpu = std::stoi(next());
         else if (k == "-d" || k == "--debug") a.debug = v.empty() ? true : (v == "true" || v == "1");
         else if (k == "--dry-run") a.dry_run = true;
+        else if (k == "--recipe") {
+            a.recipe = next();
+            if (a.recipe != "reference" && a.recipe != "declared")
+                throw std::runtime_error("--recipe '" + a.recipe + "': expected reference or declared");
+        }
         else if (k == "--tensorboard") {
             std::string t = (!v.empty() || (i + 1 < argc && argv[i + 1][0] != '-')) ? next() : "true";
             a.tensorboard = t == "true" || t == "1";
@@ -124,7 +137,76 @@ struct Config {   // the TrainingConfig fields the step uses (trainer.h:24-92)
     int num_gpus = 1;
     std::vector<int> gpu_ids;
     std::string backend = "nccl";
+    // the declared recipe: only its recipe fields are used (trainer.hpp Config; optimization.recipe turns it on)
+    TensorBoardTrainerEnhanced::Config recipe;
+    // as written in the YAML; checked (check_recipe) only when the recipe is declared
+    std::string recipe_mode = "reference", metric_mode;
+    std::vector<float> adam_betas = {0.9f, 0.999f};
 };
+
+// optimization.* / early_stopping / checkpointing / validation / ema keys of the declared recipe
+// (TrainingConfig, trainer.h:24-92; configs/train_config_recipe.yaml).  Read always and never refused here:
+// with the reference recipe these keys are ignored, whatever they hold; check_recipe judges a declared one.
+void load_recipe(const yaml_lite::Node& y, Config& c) {
+    TensorBoardTrainerEnhanced::Config& r = c.recipe;
+    if (auto& o = y["optimization"]) {
+        c.recipe_mode = o["recipe"].as<std::string>("reference");
+        r.recipe_declared = c.recipe_mode != "reference";   // anything but the default is judged by check_recipe
+        r.optimizer = o["optimizer"].as<std::string>("adam");
+        r.momentum = o["momentum"].as<float>(0.9f);
+        if (auto& a = o["adam"]) {
+            c.adam_betas = a["betas"].as<std::vector<float>>({0.9f, 0.999f});
+            r.adam_eps = a["eps"].as<float>(1e-8f);
+        }
+        r.lr_scheduler = o["lr_scheduler"].as<std::string>("none");
+        r.lr_step_size = o["lr_step_size"].as<int>(30);
+        r.lr_gamma = o["lr_gamma"].as<float>(0.1f);
+        r.lr_warmup_epochs = o["lr_warmup_epochs"].as<int>(0);
+        r.lr_min = o["lr_min"].as<float>(0.f);
+    }
+    if (auto& e = y["early_stopping"]) {
+        r.use_early_stopping = e["enabled"].as<bool>(true);
+        r.early_stop_patience = e["patience"].as<int>(20);
+        r.early_stop_min_delta = e["min_delta"].as<float>(0.f);
+    }
+    if (auto& k = y["checkpointing"]) {
+        r.save_best_only = k["save_best_only"].as<bool>(false);
+        r.keep_last_n_checkpoints = k["keep_last_n"].as<int>(0);
+    }
+    if (auto& v = y["validation"]) {
+        r.metric_to_monitor = v["primary_metric"].as<std::string>("abs_rel");
+        const std::string& m = r.metric_to_monitor;
+        const bool accuracy = m == "a1" || m == "a2" || m == "a3" || m == "delta_1.25";
+        c.metric_mode = v["metric_mode"].as<std::string>(accuracy ? "max" : "min");
+        r.metric_lower_is_better = c.metric_mode != "max";
+    }
+    if (auto& e = y["ema"])
+        r.ema_decay = e["enabled"].as<bool>(true) ? e["decay"].as<float>(0.999f) : 0.f;
+}
+
+// the resolved recipe, or "Error: optimization.<key> '<value>' ..." before any GPU call
+void check_recipe(Config& c) {
+    auto& r = c.recipe;
+    if (!r.recipe_declared) return;
+    if (c.recipe_mode != "reference" && c.recipe_mode != "declared")
+        throw std::runtime_error("optimization.recipe '" + c.recipe_mode + "': expected reference or declared");
+    if (c.adam_betas.size() != 2) throw std::runtime_error("optimization.adam.betas: expected two values");
+    r.adam_betas[0] = c.adam_betas[0];
+    r.adam_betas[1] = c.adam_betas[1];
+    if (!c.metric_mode.empty() && c.metric_mode != "min" && c.metric_mode != "max")
+        throw std::runtime_error("validation.metric_mode '" + c.metric_mode + "': expected min or max");
+    if (r.optimizer != "adam" && r.optimizer != "adamw" && r.optimizer != "sgd")
+        throw std::runtime_error("optimization.optimizer '" + r.optimizer + "': expected adam, adamw or sgd");
+    if (r.lr_scheduler != "none" && r.lr_scheduler != "step" && r.lr_scheduler != "cosine")
+        throw std::runtime_error("optimization.lr_scheduler '" + r.lr_scheduler + "': expected none, step or cosine" +
+                                 (r.lr_scheduler == "plateau" ? " (plateau is not built: no patience key is declared for it)" : ""));
+    if (r.lr_scheduler == "step" && r.lr_step_size < 1)
+        throw std::runtime_error("optimization.lr_step_size '" + std::to_string(r.lr_step_size) + "': must be at least 1");
+    if (r.ema_decay != 0.f && c.architecture == "geometry_aware")
+        throw std::runtime_error("ema: the weight average is built for the U-Net family only; set ema.enabled: false for "
+                                 "model.architecture geometry_aware");
+    TensorBoardTrainerEnhanced::checkRecipe(r, c.distributed);
+}
 
 Config load_config(const yaml_lite::Node& y, const std::string& experiment) {   // train_main.cpp:60-167
     Config c;
@@ -220,6 +302,7 @@ Config load_config(const yaml_lite::Node& y, const std::string& experiment) {   
     }
     c.checkpoint_dir += "/" + c.experiment_name;   // :163-164
     c.log_dir += "/" + c.experiment_name;
+    load_recipe(y, c);
     return c;
 }
 
@@ -387,7 +470,21 @@ int dry_run(const Config& c, const Rank& r, bool tensorboard) {
     for (int i = 0; i < nb; ++i) o << (i ? ", " : "") << "[" << boff[i] << ", " << bcnt[i] << ", " << blast[i] << "]";
     o << "]";
     // the lead rank's TensorBoard event directory ("" when it writes none)
-    o << ", \"event_dir\": \"" << (tensorboard && r.rank == 0 ? c.tensorboard_dir + "/" + c.experiment_name : std::string()) << "\"}";
+    o << ", \"event_dir\": \"" << (tensorboard && r.rank == 0 ? c.tensorboard_dir + "/" + c.experiment_name : std::string()) << "\"";
+    if (c.recipe.recipe_declared) {   // the resolved recipe and every epoch's learning rate (cad_lr_at)
+        const auto& rc = c.recipe;
+        o << ", \"recipe\": {\"optimizer\": \"" << rc.optimizer << "\", \"lr_scheduler\": \"" << rc.lr_scheduler
+          << "\", \"lr_warmup_epochs\": " << rc.lr_warmup_epochs << ", \"weight_decay\": " << float_text(rc.weight_decay)
+          << ", \"momentum\": " << float_text(rc.momentum) << ", \"ema_decay\": " << float_text(rc.ema_decay)
+          << ", \"early_stopping\": " << (rc.use_early_stopping ? "true" : "false") << ", \"patience\": " << rc.early_stop_patience
+          << ", \"metric\": \"" << rc.metric_to_monitor << "\", \"lower_is_better\": " << (rc.metric_lower_is_better ? "true" : "false")
+          << ", \"save_best_only\": " << (rc.save_best_only ? "true" : "false") << ", \"keep_last_n\": " << rc.keep_last_n_checkpoints
+          << ", \"learning_rates\": [";
+        for (int e = 1; e <= rc.num_epochs; ++e)
+            o << (e > 1 ? ", " : "") << float_text(TensorBoardTrainerEnhanced::learningRateAt(rc, e));
+        o << "]}";
+    }
+    o << "}";
     std::cout << o.str() << std::endl;
     return 0;
 }
@@ -399,6 +496,14 @@ int run(const Args& args) {
         c.num_epochs = y["debug"]["num_epochs"].as<int>(2);
         c.log_interval = y["debug"]["log_interval"].as<int>(1);
     }
+    if (!args.recipe.empty()) {   // the flag overrides the config's optimization.recipe
+        c.recipe_mode = args.recipe;
+        c.recipe.recipe_declared = args.recipe == "declared";
+    }
+    c.recipe.num_epochs = c.num_epochs;   // what the schedule and the decay are functions of
+    c.recipe.learning_rate = c.learning_rate;
+    c.recipe.weight_decay = c.weight_decay;
+    check_recipe(c);
     if (c.distributed && c.backend != "nccl" && c.backend != "rccl")
         throw std::runtime_error("hardware.backend '" + c.backend + "': this build exchanges gradients over RCCL (\"nccl\")");
     if (c.distributed && c.num_gpus > 1 && !std::getenv(kEnvRank)) return launch_ranks(args, c);
@@ -423,6 +528,10 @@ int run(const Args& args) {
     if (args.dry_run) return dry_run(c, R, args.tensorboard);
     const bool lead = R.rank == 0;   // logs, validation and checkpoints (rank 0's replica)
     if (lead) std::cout << "Loading configuration from: " << args.config << "\n";
+    if (lead && c.recipe.recipe_declared)
+        std::cout << "Recipe (declared): optimizer " << c.recipe.optimizer << ", lr_scheduler " << c.recipe.lr_scheduler
+                  << " (warmup " << c.recipe.lr_warmup_epochs << " epochs), ema decay " << c.recipe.ema_decay
+                  << ", early stopping " << (c.recipe.use_early_stopping ? "on" : "off") << "\n";
     if (args.debug && lead) std::cout << "Debug mode enabled - using reduced dataset\n";
     int ndev = 0;
     cad::check(cad_device_count(&ndev), "device query");
@@ -469,7 +578,7 @@ int run(const Args& args) {
                   << ", attention " << c.use_attention << "), parameters: " << geo->count_parameters()
                   << "\nUsing MI355X device " << R.device << "\nTraining samples: " << c.n_train
                   << (real ? " (" + c.manifest_path + ")" : std::string(" (synthetic)")) << "\n";
-        TensorBoardTrainerEnhanced::Config gc;
+        TensorBoardTrainerEnhanced::Config gc = c.recipe;   // the recipe fields; the rest as the reference sets them
         gc.num_epochs = c.num_epochs;
         gc.batch_size = c.batch_size;
         gc.learning_rate = c.learning_rate;
@@ -512,7 +621,7 @@ int run(const Args& args) {
                   << "Training samples: " << c.n_train << (real ? " (" + c.manifest_path + ")" : std::string(" (synthetic)"))
                   << ", validation samples: " << (real ? std::min(500, c.n_train) : c.n_val) << "\n";
 
-    TensorBoardTrainerEnhanced::Config tc;   // train_main.cpp:436-458
+    TensorBoardTrainerEnhanced::Config tc = c.recipe;   // train_main.cpp:436-458 (+ the recipe fields)
     tc.num_epochs = c.num_epochs;
     tc.batch_size = c.batch_size;
     tc.learning_rate = c.learning_rate;
@@ -538,7 +647,7 @@ int run(const Args& args) {
             if (ends_with(args.resume, ".pt"))   // a torch::save model archive (ours or the reference's)
                 std::cout << "Loaded model weights from " << args.resume << " (optimizer state starts fresh)\n";
             else
-                std::cout << "Resumed from " << args.resume << " (optimizer step " << trainer.optimizer().step_count() << ")\n";
+                std::cout << "Resumed from " << args.resume << " (optimizer step " << trainer.optimizer_step_count() << ")\n";
         }
     }
     trainer.train(train_loader, val_loader);

@@ -1838,6 +1838,133 @@ cad_status cad_adam_set_step_count(cad_adam* a, int64_t step) {
     });
 }
 
+// ---- the declared recipe: Adam / AdamW / SGD with an optional fused EMA (cad.h) ----
+struct cad_optim {
+    cad_unet* model = nullptr;
+    cad_optim_opts o{};
+    float *m = nullptr, *v = nullptr, *ema = nullptr;
+    int64_t step = 0;
+    bool swapped = false;   // the parameter slab holds the average, the EMA slab the raw weights
+};
+
+cad_status cad_optim_create(cad_unet* model, const cad_optim_opts* o, cad_optim** out) {
+    return guard([&] {
+        require(model && o && out, "null argument");
+        require(o->rule == CAD_OPTIM_ADAM || o->rule == CAD_OPTIM_ADAMW || o->rule == CAD_OPTIM_SGD,
+                "unknown optimizer rule " + std::to_string(o->rule));
+        require(o->ema_decay >= 0.f && o->ema_decay < 1.f, "ema_decay must be in [0, 1)");
+        HIPCHK(hipSetDevice(model->device));
+        std::unique_ptr<cad_optim, void (*)(cad_optim*)> a(new cad_optim(), cad_optim_destroy);
+        a->model = model;
+        a->o = *o;
+        a->o.ema_decay = 0.f;
+        const size_t bytes = sizeof(float) * model->n_flat;
+        HIPCHK(hipMalloc(&a->m, bytes));
+        HIPCHK(hipMemset(a->m, 0, bytes));
+        if (o->rule != CAD_OPTIM_SGD) {
+            HIPCHK(hipMalloc(&a->v, bytes));
+            HIPCHK(hipMemset(a->v, 0, bytes));
+        }
+        if (o->ema_decay > 0.f && cad_optim_attach_ema(a.get(), o->ema_decay, nullptr) != CAD_OK)
+            throw std::runtime_error(g_err);
+        *out = a.release();
+    });
+}
+void cad_optim_destroy(cad_optim* a) {
+    if (!a) return;
+    (void)hipFree(a->m);
+    (void)hipFree(a->v);
+    (void)hipFree(a->ema);
+    delete a;
+}
+cad_status cad_optim_attach_ema(cad_optim* a, float decay, void* stream) {
+    return guard([&] {
+        require(a, "null argument");
+        require(decay > 0.f && decay < 1.f, "ema_decay must be in (0, 1)");
+        require(!a->swapped, "attach_ema while the averaged weights are swapped in", CAD_ERR_INVALID);
+        cad_unet* h = a->model;
+        HIPCHK(hipSetDevice(h->device));
+        if (!a->ema) HIPCHK(hipMalloc(&a->ema, sizeof(float) * h->n_flat));
+        HIPCHK(hipMemcpyAsync(a->ema, h->flat_p, sizeof(float) * h->n_flat, hipMemcpyDeviceToDevice, S(stream)));
+        if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
+        a->o.ema_decay = decay;
+    });
+}
+cad_status cad_optim_step(cad_optim* a, void* stream) {
+    return guard([&] {
+        require(a, "null argument");
+        require(!a->swapped, "optimizer step while the averaged weights are swapped in (call ema_swap again first)",
+                CAD_ERR_INVALID);
+        cad_unet* h = a->model;
+        HIPCHK(hipSetDevice(h->device));
+        cad::optim_step(a->o.rule, h->flat_p, h->flat_g, a->m, a->v, a->ema, h->n_flat, h->norm_coef, a->o.lr, a->o.beta1,
+                        a->o.beta2, a->o.eps, a->o.weight_decay, a->o.momentum, a->o.ema_decay, (int)(a->step + 1),
+                        S(stream));
+        HIPCHK(hipGetLastError());
+        a->step += 1;
+    });
+}
+cad_status cad_optim_set_lr(cad_optim* a, float lr) {
+    return guard([&] {
+        require(a, "null argument");
+        a->o.lr = lr;
+    });
+}
+// null handle: 0 / -1 / -1 (no status to return one in)
+float cad_optim_lr(const cad_optim* a) { return a ? a->o.lr : 0.f; }
+int cad_optim_rule(const cad_optim* a) { return a ? a->o.rule : -1; }
+int64_t cad_optim_step_count(const cad_optim* a) { return a ? a->step : -1; }
+cad_status cad_optim_set_step_count(cad_optim* a, int64_t step) {
+    return guard([&] {
+        require(a, "null argument");
+        require(step >= 0, "negative step");
+        a->step = step;
+    });
+}
+cad_status cad_optim_state(cad_optim* a, float** m, float** v, float** ema) {
+    return guard([&] {
+        require(a, "null argument");
+        if (m) *m = a->m;
+        if (v) *v = a->v;
+        if (ema) *ema = a->ema;
+    });
+}
+cad_status cad_optim_ema_swap(cad_optim* a, void* stream) {
+    return guard([&] {
+        require(a && a->ema, "ema_swap: no EMA attached (ema_decay 0)");
+        cad_unet* h = a->model;
+        HIPCHK(hipSetDevice(h->device));
+        cad::slab_swap(h->flat_p, a->ema, h->n_flat, S(stream));
+        HIPCHK(hipGetLastError());
+        a->swapped = !a->swapped;
+    });
+}
+int cad_optim_swapped(const cad_optim* a) { return a && a->swapped ? 1 : 0; }
+
+cad_status cad_lr_at(const cad_lr_opts* o, int epoch0, int num_epochs, float* lr) {
+    return guard([&] {
+        require(o && lr, "null argument");
+        const std::string name = o->scheduler ? o->scheduler : "none";
+        require(name == "none" || name == "step" || name == "cosine",
+                "lr_scheduler '" + name + "': expected none, step or cosine" +
+                    (name == "plateau" ? " (plateau is not built: the reference declares no patience for it)" : ""));
+        require(epoch0 >= 0, "negative epoch");
+        const int W = std::max(0, o->warmup_epochs);
+        const double base = (double)o->lr, t = (double)(epoch0 - W);
+        double r = base;
+        if (epoch0 < W) {
+            r = base * (double)(epoch0 + 1) / (double)W;
+        } else if (name == "step") {
+            require(o->step_size >= 1, "lr_step_size must be >= 1");
+            r = base * std::pow((double)o->gamma, std::floor(t / (double)o->step_size));
+        } else if (name == "cosine") {
+            const double T = (double)std::max(1, num_epochs - W), lo = (double)o->lr_min;
+            r = lo + (base - lo) * (1.0 + std::cos(M_PI * t / T)) / 2.0;
+        }
+        *lr = (float)r;
+    });
+}
+
 cad_status cad_loss_create(float si, float gr, float sm, float rp, int max_batch, int height, int width, int device,
                            cad_loss** out) {
     return guard([&] {

@@ -924,6 +924,19 @@ cad_status cad_geonet_adam_step(cad_geonet* h, float lr, float beta1, float beta
     });
 }
 
+cad_status cad_geonet_optim_step(cad_geonet* h, const cad_optim_opts* o, void* stream) {
+    return gguard([&] {
+        need(h && o, "null argument");
+        need(o->rule == CAD_OPTIM_ADAM || o->rule == CAD_OPTIM_ADAMW || o->rule == CAD_OPTIM_SGD, "unknown optimizer rule");
+        need(o->ema_decay == 0.f, "ema: the weight average is built for the U-Net family only (ema_decay must be 0 here)");
+        GCHK(hipSetDevice(h->device));
+        ++h->adam_t;
+        cad::optim_step(o->rule, h->flat_p, h->flat_g, h->adam_m, h->adam_v, nullptr, h->n_flat, h->norm_coef, o->lr,
+                        o->beta1, o->beta2, o->eps, o->weight_decay, o->momentum, 0.f, (int)h->adam_t, S(stream));
+        GCHK(hipGetLastError());
+    });
+}
+
 int64_t cad_geonet_num_batches_tracked(const cad_geonet* h, int film) { return h ? (film ? h->nbt_film : h->nbt) : -1; }
 
 // ---- operator-level entry points (tests): one CBAM / one PCL forward + backward on device tensors.

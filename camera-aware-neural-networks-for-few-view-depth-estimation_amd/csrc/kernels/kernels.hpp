@@ -394,6 +394,14 @@ void grad_norm_clip(const float* g, int64_t n, float max_norm, float prescale, d
                     float* norm_coef, hipStream_t st);
 void adam_step(float* p, float* g, float* m, float* v, int64_t n, const float* norm_coef, float lr,
                float b1, float b2, float eps, float wd, int step, hipStream_t st);
+// the declared recipe's update rules (CAD_OPTIM_* of cad.h) in one pass shaped like adam_step; kOptimAdam
+// without an EMA slab gives adam_step's bits.  v: unused by kOptimSGD (may be null); ema: null = none,
+// else ema = ema_d ema + (1 - ema_d) p_new in the same pass
+enum { kOptimAdam = 0, kOptimAdamW = 1, kOptimSGD = 2 };
+void optim_step(int rule, float* p, float* g, float* m, float* v, float* ema, int64_t n, const float* norm_coef,
+                float lr, float b1, float b2, float eps, float wd, float mu, float ema_d, int step, hipStream_t st);
+// exchange two slabs of n floats in place
+void slab_swap(float* a, float* b, int64_t n, hipStream_t st);
 
 // ---------------- batch assembly (batch_kernels.hip) ----------------
 // One decoded sample and what the loader does to it (sunrgbd_loader.cpp resizeSample / augmentSample);

@@ -10,6 +10,8 @@ the reference's own code:
                           FiLM blocks after (intrinsics_unet.h:16-113)
   CombinedDepthLoss       CombinedDepthLoss          src/loss/depth_loss.h:366-479
   Adam                    torch::optim::Adam         (options built at tensorboard_trainer_enhanced.h:97-101)
+  Optimizer               torch::optim::Adam / AdamW / SGD by rule (src/training/trainer.h:388-414), with an
+                          optional EMA of the weights kept in the same pass (no reference counterpart)
   clip_grad_norm_         torch::nn::utils::clip_grad_norm_ (enhanced.h:300-302)
   Trainer.train_step      TensorBoardTrainerEnhanced::trainEpoch body, enhanced.h:287-304
 
@@ -327,6 +329,77 @@ class Adam:
         h = getattr(self, "h", None)
         if h is not None and h.value:
             self.lib.cad_adam_destroy(h)
+            self.h = None
+
+
+class Optimizer:
+    """The declared recipe's update rules over a U-Net's flat slab (cad_optim_*): rule "adam" (torch::optim::Adam,
+    coupled L2 — the bits of `Adam` above), "adamw" (torch::optim::AdamW) or "sgd" (torch::optim::SGD with
+    momentum and weight decay), trainer.h:388-414.  ema_decay > 0 keeps an exponential moving average of the
+    weights in the same pass (ours; the reference has none): ema = d ema + (1 - d) p after every step, started
+    as a copy of the parameters."""
+
+    def __init__(self, model: BaselineUNet, rule="adam", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 momentum=0.0, ema_decay=0.0):
+        if not isinstance(model, BaselineUNet):   # model.h is passed on as a cad_unet*
+            raise TypeError(f"cad.Optimizer serves the U-Net family (BaselineUNet and its subclasses), not "
+                            f"{type(model).__name__}: the geometry-aware networks take train_step(rule=...) / optim_step, "
+                            "without an EMA")
+        if rule not in _abi.OPTIM_RULES:
+            raise ValueError(f"rule must be one of {tuple(_abi.OPTIM_RULES)}, not {rule!r}")
+        self.model, self.lib, self.rule = model, model.lib, rule
+        torch.cuda.synchronize(model.device)   # the EMA starts as a copy of the parameters as they are now
+        o = _abi.OptimOpts(_abi.OPTIM_RULES[rule], lr, betas[0], betas[1], eps, weight_decay, momentum, ema_decay)
+        h = C.c_void_p()
+        check(self.lib.cad_optim_create(model.h, C.byref(o), C.byref(h)), "cad_optim_create")
+        self.h = h
+
+    def step(self):
+        check(self.lib.cad_optim_step(self.h, _stream(self.model.device)), "cad_optim_step")
+
+    def zero_grad(self):
+        """No-op: every backward overwrites the whole gradient slab (set_to_none semantics)."""
+
+    def set_lr(self, lr):
+        check(self.lib.cad_optim_set_lr(self.h, float(lr)), "set_lr")
+
+    @property
+    def lr(self) -> float:
+        return float(self.lib.cad_optim_lr(self.h))
+
+    @property
+    def step_count(self) -> int:
+        return int(self.lib.cad_optim_step_count(self.h))
+
+    def state(self) -> dict:
+        """Views of the device state slabs in the flat layout: m (sgd: the momentum buffer), v (None for sgd),
+        ema (None without one)."""
+        m, v, e = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self.lib.cad_optim_state(self.h, C.byref(m), C.byref(v), C.byref(e)), "cad_optim_state")
+        view = lambda p: _flat_view(p.value, self.model.n_flat, self.model.device) if p.value else None  # noqa: E731
+        return {"m": view(m), "v": view(v), "ema": view(e), "step": self.step_count}
+
+    @property
+    def ema(self):
+        """The averaged weights, a view of the EMA slab in the flat_params layout (None without one)."""
+        return self.state()["ema"]
+
+    def attach_ema(self, decay):
+        """(Re)start the average as a copy of the current parameters."""
+        check(self.lib.cad_optim_attach_ema(self.h, float(decay), _stream(self.model.device)), "attach_ema")
+
+    def ema_swap(self):
+        """Exchange the parameter and EMA slabs in place: evaluate or save the averaged model between two swaps."""
+        check(self.lib.cad_optim_ema_swap(self.h, _stream(self.model.device)), "ema_swap")
+
+    @property
+    def swapped(self) -> bool:
+        return bool(self.lib.cad_optim_swapped(self.h))
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            self.lib.cad_optim_destroy(h)
             self.h = None
 
 
@@ -730,9 +803,25 @@ class Trainer:
     build/train."""
 
     def __init__(self, model: BaselineUNet, loss_fn: CombinedDepthLoss, lr=1e-4, weight_decay=1e-5,
-                 grad_clip=1.0, use_grad_clip=True, process_group=None, bucket_mb=25.0, communicator=None):
+                 grad_clip=1.0, use_grad_clip=True, process_group=None, bucket_mb=25.0, communicator=None,
+                 optimizer="adam", schedule=None, ema_decay=0.0, momentum=0.0, betas=(0.9, 0.999), eps=1e-8):
+        """optimizer / schedule / ema_decay are the declared recipe (off by default: the reference's Adam at a
+        constant rate).  schedule: None, a callable step -> lr, or a dict of lr_at() keywords plus num_epochs
+        and steps_per_epoch (the per-epoch schedule of build/train); it is applied before every step."""
         self.model, self.loss_fn = model, loss_fn
-        self.optimizer = Adam(model, lr=lr, weight_decay=weight_decay)
+        if optimizer == "adam" and ema_decay == 0.0 and momentum == 0.0 and tuple(betas) == (0.9, 0.999) and eps == 1e-8:
+            self.optimizer = Adam(model, lr=lr, weight_decay=weight_decay)
+        else:
+            self.optimizer = Optimizer(model, rule=optimizer, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                       momentum=momentum, ema_decay=ema_decay)
+        if isinstance(schedule, dict):
+            from .recipe import lr_at
+            kw = dict(schedule)
+            num_epochs, spe = int(kw.pop("num_epochs")), int(kw.pop("steps_per_epoch"))
+            lr_at(0, num_epochs, lr, **kw)   # an unknown scheduler fails here, not at the first step
+            schedule = lambda k: lr_at(min(k // spe, num_epochs - 1), num_epochs, lr, **kw)  # noqa: E731
+        self.schedule = schedule
+        self.steps = 0
         self.grad_clip = grad_clip if use_grad_clip else float("inf")
         self.pg = process_group
         self.comm = communicator
@@ -814,7 +903,10 @@ class Trainer:
         else:
             m.backward(self.dpred)
             clip_grad_norm_(m, self.grad_clip)
+        if self.schedule is not None:
+            self.optimizer.set_lr(self.schedule(self.steps))
         self.optimizer.step()
+        self.steps += 1
         return self.loss5
 
 
@@ -1108,18 +1200,30 @@ class GeometryAwareNetwork(ResNetUNet):
 
     def train_step(self, loss_fn: "CombinedDepthLoss", rgb, gt, K, lr=1e-4, weight_decay=1e-5, grad_clip=1.0,
                    rays=None, pred=None, dpred=None, loss5=None, process_group=None, communicator=None,
-                   bucket_mb=25.0):
+                   bucket_mb=25.0, rule=None, momentum=0.0, betas=(0.9, 0.999), eps=1e-8):
         """One optimisation step (enhanced.h:287-304 sequence) fed the loader's batch: rays default to
         RayDirectionComputer's from K (a18), intrinsics = [K00, K11, K02, K12] (a15).  Data-parallel
-        exchange as ResNetUNet.train_step."""
+        exchange as ResNetUNet.train_step.  rule: None = the reference's Adam (adam_step); "adam" / "adamw" /
+        "sgd" = the declared recipe's rules (optim_step; keep to one rule per model)."""
         if rays is None:
             rays = ray_directions(K, rgb.shape[2], rgb.shape[3])
         pred = self.forward(rgb, rays, camera_from_K(K), out=pred)
         loss5, dpred = loss_fn.forward_with_intrinsics(pred, gt, rgb, K, loss5=loss5, dpred=dpred)
         world = self._exchange_backward(dpred, process_group, communicator, bucket_mb)
         self.clip_grad_norm_(grad_clip if grad_clip else float("inf"), 1.0 / world)
-        self.adam_step(lr=lr, weight_decay=weight_decay)
+        if rule is None:
+            self.adam_step(lr=lr, weight_decay=weight_decay)
+        else:
+            self.optim_step(rule, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum=momentum)
         return loss5, pred
+
+    def optim_step(self, rule, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, momentum=0.0, ema_decay=0.0):
+        """cad_geonet_optim_step: one step of "adam" / "adamw" / "sgd" on the in-handle moments (the EMA is
+        U-Net-family only: ema_decay != 0 is refused)."""
+        if rule not in _abi.OPTIM_RULES:
+            raise ValueError(f"rule must be one of {tuple(_abi.OPTIM_RULES)}, not {rule!r}")
+        o = _abi.OptimOpts(_abi.OPTIM_RULES[rule], lr, betas[0], betas[1], eps, weight_decay, momentum, ema_decay)
+        check(self.lib.cad_geonet_optim_step(self.h, C.byref(o), _stream(self.device)), "cad_geonet_optim_step")
 
 
 class LightweightGeometryNetwork(GeometryAwareNetwork):

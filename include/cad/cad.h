@@ -29,6 +29,11 @@
  *   cad_clip_grad_norm              torch::nn::utils::clip_grad_norm_         enhanced.h:300-302
  *   cad_adam_create/step            torch::optim::Adam(AdamOptions(lr).weight_decay(wd)) / step()
  *                                   enhanced.h:97-101, :304
+ *   cad_optim_create/step           Trainer::createOptimizer: torch::optim::Adam / AdamW / SGD by
+ *   cad_geonet_optim_step           TrainingConfig::optimizer      src/training/trainer.h:388-414, step :348
+ *   cad_optim_set_lr / cad_lr_at    createScheduler (StepLR / CosineAnnealingLR) and the epoch loop's warmup
+ *                                   and scheduler.step()           trainer.h:416-431, :262-308
+ *   cad_optim_attach_ema/ema_swap   exponential moving average of the weights (new: no reference counterpart)
  *   cad_unet_flat                   flat gradient slab for the data-parallel RCCL all-reduce (new:
  *                                   the reference is single-device)
  *   cad_comm_* / cad_grad_allreduce / cad_unet_backward_allreduce
@@ -221,6 +226,66 @@ int64_t cad_adam_step_count(const cad_adam* a);
  * floats each, same packed layout as the parameters) and the step counter */
 cad_status cad_adam_state(cad_adam* a, float** m, float** v);
 cad_status cad_adam_set_step_count(cad_adam* a, int64_t step);
+
+/* ---- the declared training recipe (trainer.h:24-92, :388-431): Adam / AdamW / SGD over the model's flat
+ * slab in one pass, an optional exponential moving average of the weights fused into it (ours: the
+ * reference has none), and the per-epoch learning-rate schedule.  cad_adam_* above is unchanged;
+ * CAD_OPTIM_ADAM without an EMA gives its bits. ----
+ *   CAD_OPTIM_ADAM   torch::optim::Adam, coupled L2 (g += wd p)
+ *   CAD_OPTIM_ADAMW  torch::optim::AdamW: p *= 1 - lr wd, then Adam on the bare gradient (decay uniform over
+ *                    the slab, as AdamW over parameters(); zero padding stays zero)
+ *   CAD_OPTIM_SGD    torch::optim::SGD(lr).momentum(mu).weight_decay(wd): g += wd p; buf = mu buf + g (zero-
+ *                    initialised: the first step gives buf = g; dampening 0, no Nesterov); p -= lr buf.
+ *                    buf lives in the m slab; there is no v slab. */
+#define CAD_OPTIM_ADAM 0
+#define CAD_OPTIM_ADAMW 1
+#define CAD_OPTIM_SGD 2
+typedef struct {
+    int rule;           /* CAD_OPTIM_* */
+    float lr;
+    float beta1, beta2; /* Adam / AdamW */
+    float eps;
+    float weight_decay;
+    float momentum;     /* SGD */
+    float ema_decay;    /* d in [0, 1): ema = d ema + (1 - d) p after every step; 0 = no EMA slab */
+} cad_optim_opts;
+typedef struct cad_optim cad_optim;
+cad_status cad_optim_create(cad_unet* model, const cad_optim_opts* opts, cad_optim** out);
+void cad_optim_destroy(cad_optim* o);
+cad_status cad_optim_step(cad_optim* o, void* stream); /* consumes the clip coefficient, as cad_adam_step */
+cad_status cad_optim_set_lr(cad_optim* o, float lr);
+float cad_optim_lr(const cad_optim* o);
+int cad_optim_rule(const cad_optim* o);
+int64_t cad_optim_step_count(const cad_optim* o);
+cad_status cad_optim_set_step_count(cad_optim* o, int64_t step);
+/* device pointers to the state slabs (cad_unet_flat's n floats each): m (SGD: the momentum buffer), v (null
+ * for SGD) and ema (null without one) */
+cad_status cad_optim_state(cad_optim* o, float** m, float** v, float** ema);
+/* (re)start the average: allocates the slab on first use and copies the current parameters into it */
+cad_status cad_optim_attach_ema(cad_optim* o, float decay, void* stream);
+/* exchange the contents of the parameter and EMA slabs in place.  Validation, panels and checkpoints of the
+ * averaged model run between two swaps; two swaps restore both slabs bit for bit.  The U-Net rebuilds its
+ * prepared weights at every forward, so nothing else needs invalidating.  cad_optim_step while swapped is
+ * CAD_ERR_INVALID. */
+cad_status cad_optim_ema_swap(cad_optim* o, void* stream);
+int cad_optim_swapped(const cad_optim* o);
+
+/* The learning rate of 0-based epoch `epoch0` out of `num_epochs` (host only, pure).  W = warmup_epochs,
+ * t = epoch0 - W, computed in double and rounded to float:
+ *   epoch0 < W: lr (epoch0 + 1) / W;  "none": lr;  "step": lr gamma^floor(t / step_size);
+ *   "cosine": lr_min + (lr - lr_min) (1 + cos(pi t / max(1, num_epochs - W))) / 2.
+ * These equal the reference's loop (trainer.h:262-308: the warmup rate set directly, scheduler.step() after
+ * each epoch >= W) over StepLR / CosineAnnealingLR(T_max = num_epochs - W, eta_min = lr_min).  "plateau" and
+ * unknown names: CAD_ERR_INVALID, the value named in cad_last_error(). */
+typedef struct {
+    float lr;
+    const char* scheduler; /* "none" | "step" | "cosine" (NULL = "none") */
+    int step_size;
+    float gamma;
+    int warmup_epochs;
+    float lr_min;
+} cad_lr_opts;
+cad_status cad_lr_at(const cad_lr_opts* opts, int epoch0, int num_epochs, float* lr);
 
 /* ---- checkpoints in the reference's format: torch::save(model_, path) / torch::load(model, path)
  * (tensorboard_trainer_enhanced.h:656-662; production_trainer.h:323-330 writes final_model.pt).
@@ -699,6 +764,9 @@ cad_status cad_geonet_clip_grad_norm(cad_geonet* h, float max_norm, float presca
 cad_status cad_geonet_last_grad_norm(cad_geonet* h, float* total_norm, void* stream);
 cad_status cad_geonet_adam_step(cad_geonet* h, float lr, float beta1, float beta2, float eps, float weight_decay,
                                 void* stream);
+/* one step of opts->rule (CAD_OPTIM_*) at opts->lr on the in-handle moments (SGD's buffer in the first-moment
+ * slab); keep to one rule per handle.  The EMA is U-Net-family only: opts->ema_decay != 0 is CAD_ERR_INVALID */
+cad_status cad_geonet_optim_step(cad_geonet* h, const cad_optim_opts* opts, void* stream);
 /* BatchNorm num_batches_tracked: film = 0 the BatchNorm2d layers, 1 FiLM's BatchNorm1d (B > 1 only) */
 int64_t cad_geonet_num_batches_tracked(const cad_geonet* h, int film);
 /* operator-level entry points (tests; state allocated per call): one CBAMImpl forward + backward

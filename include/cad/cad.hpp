@@ -315,6 +315,10 @@ public:
                    void* stream = nullptr) {
         cad::check(cad_geonet_adam_step(h_, lr, beta1, beta2, eps, weight_decay, stream), "adam_step");
     }
+    // one step of the declared recipe's rule (o.rule: CAD_OPTIM_*) at o.lr; an EMA is refused here
+    void optim_step(const cad_optim_opts& o, void* stream = nullptr) {
+        cad::check(cad_geonet_optim_step(h_, &o, stream), "optim_step");
+    }
     int64_t count_parameters() const { return cad_geonet_count_parameters(h_); }
     void train(bool on = true) {
         cad::check(cad_geonet_train(h_, on ? 1 : 0), "train");
@@ -478,6 +482,64 @@ public:
 
 private:
     cad_adam* h_ = nullptr;
+};
+
+// The declared recipe's optimizers (trainer.h:388-414) over the same slab, the rule chosen at run time:
+// "adam" (the arithmetic of Adam above), "adamw" (torch::optim::AdamW), "sgd" (torch::optim::SGD with momentum
+// and weight decay).  attach_ema(d) keeps ema = d ema + (1 - d) p in the step's own pass (ours: the reference
+// has no average); ema_swap() exchanges the parameter and EMA slabs so that validation, panels and
+// checkpoints of the averaged model run between two swaps.
+class Optimizer {
+public:
+    static int rule_of(const std::string& name) {
+        if (name == "adam") return CAD_OPTIM_ADAM;
+        if (name == "adamw") return CAD_OPTIM_ADAMW;
+        if (name == "sgd") return CAD_OPTIM_SGD;
+        throw std::runtime_error("optimizer '" + name + "': expected adam, adamw or sgd");
+    }
+    static const char* rule_name(int rule) {
+        return rule == CAD_OPTIM_ADAM ? "adam" : rule == CAD_OPTIM_ADAMW ? "adamw" : rule == CAD_OPTIM_SGD ? "sgd" : "?";
+    }
+    Optimizer(BaselineUNetImpl& model, const cad_optim_opts& o) : opts_(o) {
+        cad::check(cad_optim_create(model.handle(), &o, &h_), "Optimizer");
+    }
+    Optimizer(BaselineUNetImpl& model, const std::string& rule, float lr, float weight_decay = 0.f, float momentum = 0.f,
+              float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, float ema_decay = 0.f)
+        : Optimizer(model, cad_optim_opts{rule_of(rule), lr, beta1, beta2, eps, weight_decay, momentum, ema_decay}) {}
+    virtual ~Optimizer() { cad_optim_destroy(h_); }
+    Optimizer(const Optimizer&) = delete;
+    Optimizer& operator=(const Optimizer&) = delete;
+    void zero_grad() {}   // every backward overwrites the gradient slab
+    void step(void* stream = nullptr) { cad::check(cad_optim_step(h_, stream), "Optimizer::step"); }
+    void set_lr(float lr) { cad::check(cad_optim_set_lr(h_, lr), "set_lr"); }
+    float lr() const { return cad_optim_lr(h_); }
+    int rule() const { return cad_optim_rule(h_); }
+    const cad_optim_opts& options() const { return opts_; }   // as created (the rate then follows set_lr)
+    int64_t step_count() const { return cad_optim_step_count(h_); }
+    void set_step_count(int64_t s) { cad::check(cad_optim_set_step_count(h_, s), "set_step_count"); }
+    void attach_ema(float decay, void* stream = nullptr) {
+        cad::check(cad_optim_attach_ema(h_, decay, stream), "attach_ema");
+        opts_.ema_decay = decay;
+    }
+    bool has_ema() const { return opts_.ema_decay > 0.f; }
+    void ema_swap(void* stream = nullptr) { cad::check(cad_optim_ema_swap(h_, stream), "ema_swap"); }
+    bool swapped() const { return cad_optim_swapped(h_) != 0; }
+    cad_optim* handle() const { return h_; }
+
+private:
+    cad_optim_opts opts_{};
+    cad_optim* h_ = nullptr;
+};
+class AdamW : public Optimizer {   // torch::optim::AdamW(params, AdamWOptions(lr).weight_decay(wd))
+public:
+    AdamW(BaselineUNetImpl& model, float lr = 1e-3f, float weight_decay = 1e-2f, float beta1 = 0.9f, float beta2 = 0.999f,
+          float eps = 1e-8f)
+        : Optimizer(model, "adamw", lr, weight_decay, 0.f, beta1, beta2, eps) {}
+};
+class SGD : public Optimizer {   // torch::optim::SGD(params, SGDOptions(lr).momentum(mu).weight_decay(wd))
+public:
+    SGD(BaselineUNetImpl& model, float lr, float momentum = 0.f, float weight_decay = 0.f)
+        : Optimizer(model, "sgd", lr, weight_decay, momentum) {}
 };
 }  // namespace optim
 

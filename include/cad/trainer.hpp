@@ -21,7 +21,13 @@
 //     rank r trains its batch_size-slice of every global batch, gradients are SUM-all-reduced in
 //     buckets overlapped with the backward and clipped as the mean; rank 0 validates, logs and saves;
 //   * logLossComponents reads sample 0 without augmentation (the reference's getSample(0) draws from
-//     the augmentation rng).
+//     the augmentation rng);
+//   * Config::recipe_declared (off by default) runs the recipe the reference declares in TrainingConfig / Trainer
+//     (src/training/trainer.h:24-92, :262-316, :388-431, :461-467) and never executes: Adam / AdamW / SGD, a
+//     per-epoch learning rate (warmup, step or cosine: cad_lr_at), checkImprovement on a monitored validation
+//     metric with best_model.*, early stopping, save_best_only and keep_last_n checkpoints — and, ours, an
+//     exponential moving average of the weights that validation, panels and <checkpoint>_ema.pt use.  With it off
+//     every file, record and line of output is what it was.
 #ifndef CAD_TRAINER_HPP
 #define CAD_TRAINER_HPP
 
@@ -286,18 +292,47 @@ inline GradientStats log_histograms(EventWriter* ev, int num_params, int64_t epo
     return g;
 }
 
+// The declared recipe's bookkeeping across epochs (TrainingState, trainer.h:97-110): the best monitored metric
+// so far and the validations since it last improved.  best starts at +inf (lower is better) or -inf.
+struct RecipeProgress {
+    float best_metric = std::numeric_limits<float>::infinity();
+    int32_t epochs_without_improvement = 0;
+    // checkImprovement (trainer.h:461-467): strictly better than best -/+ min_delta; updates the state
+    bool improved(float current, bool lower_is_better, float min_delta) {
+        const bool better = lower_is_better ? current < best_metric - min_delta : current > best_metric + min_delta;
+        if (better) {
+            best_metric = current;
+            epochs_without_improvement = 0;
+        } else {
+            ++epochs_without_improvement;
+        }
+        return better;
+    }
+};
+
+// a float32 with the nine significant digits that read back to the same float32
+inline std::string float_text(float v) {
+    std::ostringstream o;
+    o << std::setprecision(std::numeric_limits<float>::max_digits10) << v;
+    return o.str();
+}
+
 // .cadckpt: named parameters and buffers (reference layout) + the Adam state the reference never
 // saves (moments, step count) — a full resume.  torch::save archives (.pt) carry the weights only.
-inline void save_training_state(const std::string& path, BaselineUNetImpl& m, optim::Adam& opt) {
-    std::ofstream f(path, std::ios::binary);
-    if (!f) throw std::runtime_error("cannot write checkpoint " + path);
-    auto ps = m.named_parameters();
+// With the declared recipe the optimizer section is tagged instead ("RCPE": rule, hyper-parameters, step count
+// and the rule's state slabs), followed by "EMA_" (decay and the averaged slab, when one is kept) and "BEST"
+// (RecipeProgress); the learning rate is a function of the epoch and is not stored.  Files of the reference
+// recipe carry none of these and are byte for byte what they were.
+// the tensor block every .cadckpt starts with: the model's named parameters, then its named buffers
+template <class Model>
+inline void write_checkpoint_tensors(std::ostream& f, const Model& m) {
+    auto ts = m.named_parameters();
     auto bs = m.named_buffers();
-    ps.insert(ps.end(), bs.begin(), bs.end());
+    ts.insert(ts.end(), bs.begin(), bs.end());
     f.write("CADCKPT1", 8);
-    const int32_t n = (int32_t)ps.size();
+    const int32_t n = (int32_t)ts.size();
     f.write((const char*)&n, 4);
-    for (auto& t : ps) {
+    for (auto& t : ts) {
         const int32_t ln = (int32_t)t.name.size(), nd = (int32_t)t.shape.size();
         f.write((const char*)&ln, 4);
         f.write(t.name.data(), ln);
@@ -305,6 +340,12 @@ inline void save_training_state(const std::string& path, BaselineUNetImpl& m, op
         f.write((const char*)t.shape.data(), 8 * nd);
         f.write((const char*)t.value.data(), 4 * (int64_t)t.value.size());
     }
+}
+
+inline void save_training_state(const std::string& path, BaselineUNetImpl& m, optim::Adam& opt) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot write checkpoint " + path);
+    write_checkpoint_tensors(f, m);
     float *mp, *vp;
     int64_t nflat;
     cad::check(cad_unet_flat(m.handle(), nullptr, nullptr, &nflat), "flat");
@@ -320,7 +361,113 @@ inline void save_training_state(const std::string& path, BaselineUNetImpl& m, op
     }
 }
 
-inline void load_training_state(const std::string& path, BaselineUNetImpl& m, optim::Adam& opt) {
+// host-side writers / readers of the declared recipe's sections (no device: the slabs arrive as host arrays)
+struct RecipeSections {
+    int32_t rule = CAD_OPTIM_ADAM;
+    float hyper[5] = {0.9f, 0.999f, 1e-8f, 0.f, 0.f};   // beta1, beta2, eps, weight_decay, momentum
+    int64_t step = 0, nflat = 0;
+    std::vector<std::vector<float>> slabs;   // m [, v]
+    float ema_decay = 0.f;
+    std::vector<float> ema;                  // empty: none
+    bool have_progress = false;
+    RecipeProgress progress;
+    bool have_rule = false;                  // an "RCPE" section was read
+    bool reference_adam = false;             // an "ADAM" section (reference recipe) was read instead
+};
+inline void write_recipe_sections(std::ostream& f, const RecipeSections& s) {
+    f.write("RCPE", 4);
+    f.write((const char*)&s.rule, 4);
+    f.write((const char*)s.hyper, sizeof s.hyper);
+    f.write((const char*)&s.step, 8);
+    f.write((const char*)&s.nflat, 8);
+    const int32_t ns = (int32_t)s.slabs.size();
+    f.write((const char*)&ns, 4);
+    for (auto& v : s.slabs) f.write((const char*)v.data(), 4 * s.nflat);
+    if (!s.ema.empty()) {
+        f.write("EMA_", 4);
+        f.write((const char*)&s.ema_decay, 4);
+        f.write((const char*)&s.nflat, 8);
+        f.write((const char*)s.ema.data(), 4 * s.nflat);
+    }
+    f.write("BEST", 4);
+    f.write((const char*)&s.progress.best_metric, 4);
+    f.write((const char*)&s.progress.epochs_without_improvement, 4);
+}
+// reads every section after the tensor block until the end of the file; an "ADAM" section is kept as two slabs
+inline RecipeSections read_recipe_sections(std::istream& f, const std::string& path) {
+    RecipeSections s;
+    char tag[4];
+    auto slab = [&](std::vector<float>& v, int64_t n) {
+        if (n < 0 || n > (int64_t)1 << 34) throw std::runtime_error("corrupt section size in " + path);
+        v.resize((size_t)n);
+        f.read((char*)v.data(), 4 * n);
+    };
+    while (f.read(tag, 4)) {
+        if (std::memcmp(tag, "ADAM", 4) == 0) {
+            s.reference_adam = true;
+            f.read((char*)&s.step, 8);
+            f.read((char*)&s.nflat, 8);
+            s.slabs.resize(2);
+            for (auto& v : s.slabs) slab(v, s.nflat);
+        } else if (std::memcmp(tag, "RCPE", 4) == 0) {
+            s.have_rule = true;
+            int32_t ns = 0;
+            f.read((char*)&s.rule, 4);
+            f.read((char*)s.hyper, sizeof s.hyper);
+            f.read((char*)&s.step, 8);
+            f.read((char*)&s.nflat, 8);
+            f.read((char*)&ns, 4);
+            if (!f || ns < 1 || ns > 2) throw std::runtime_error("corrupt optimizer section in " + path);
+            s.slabs.resize((size_t)ns);
+            for (auto& v : s.slabs) slab(v, s.nflat);
+        } else if (std::memcmp(tag, "EMA_", 4) == 0) {
+            int64_t n = 0;
+            f.read((char*)&s.ema_decay, 4);
+            f.read((char*)&n, 8);
+            slab(s.ema, n);
+        } else if (std::memcmp(tag, "BEST", 4) == 0) {
+            s.have_progress = true;
+            f.read((char*)&s.progress.best_metric, 4);
+            f.read((char*)&s.progress.epochs_without_improvement, 4);
+        } else {
+            throw std::runtime_error("unknown section '" + std::string(tag, 4) + "' in " + path);
+        }
+        if (!f) throw std::runtime_error("truncated section '" + std::string(tag, 4) + "' in " + path);
+    }
+    return s;
+}
+
+inline void save_training_state(const std::string& path, BaselineUNetImpl& m, optim::Optimizer& opt,
+                                const RecipeProgress& progress) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot write checkpoint " + path);
+    write_checkpoint_tensors(f, m);
+    RecipeSections s;
+    const cad_optim_opts& o = opt.options();
+    s.rule = o.rule;
+    const float hyper[5] = {o.beta1, o.beta2, o.eps, o.weight_decay, o.momentum};
+    std::memcpy(s.hyper, hyper, sizeof hyper);
+    s.step = opt.step_count();
+    cad::check(cad_unet_flat(m.handle(), nullptr, nullptr, &s.nflat), "flat");
+    float *mp = nullptr, *vp = nullptr, *ep = nullptr;
+    cad::check(cad_optim_state(opt.handle(), &mp, &vp, &ep), "optim_state");
+    auto fetch = [&](float* src) {
+        std::vector<float> v((size_t)s.nflat);
+        cad::check(cad_memcpy(v.data(), src, 4 * s.nflat, 1, nullptr), "d2h");
+        return v;
+    };
+    s.slabs.push_back(fetch(mp));
+    if (vp) s.slabs.push_back(fetch(vp));
+    if (ep) {
+        s.ema_decay = o.ema_decay;
+        s.ema = fetch(ep);
+    }
+    s.progress = progress;
+    write_recipe_sections(f, s);
+}
+
+// opens a .cadckpt and loads its tensor block into the model; the stream is left at the first section
+inline std::ifstream load_checkpoint_tensors(const std::string& path, BaselineUNetImpl& m) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw std::runtime_error("Cannot open checkpoint: " + path);
     char magic[8];
@@ -347,8 +494,17 @@ inline void load_training_state(const std::string& path, BaselineUNetImpl& m, op
         if (!why.empty()) throw std::runtime_error(why);
     }
     if (!f || m.load(ts) != n) throw std::runtime_error("checkpoint does not match the model: " + path);
+    return f;
+}
+
+inline void load_training_state(const std::string& path, BaselineUNetImpl& m, optim::Adam& opt) {
+    std::ifstream f = load_checkpoint_tensors(path, m);
     char tag[4];
-    if (f.read(tag, 4) && std::memcmp(tag, "ADAM", 4) == 0) {
+    if (!f.read(tag, 4)) return;
+    if (std::memcmp(tag, "RCPE", 4) == 0)
+        throw std::runtime_error("checkpoint " + path + " was written by the declared recipe: resume it with "
+                                 "optimization.recipe: declared (--recipe declared)");
+    if (std::memcmp(tag, "ADAM", 4) == 0) {
         int64_t step, nflat, mine;
         f.read((char*)&step, 8);
         f.read((char*)&nflat, 8);
@@ -363,6 +519,37 @@ inline void load_training_state(const std::string& path, BaselineUNetImpl& m, op
         }
         cad::check(cad_adam_set_step_count(opt.handle(), step), "set_step");
     }
+}
+
+// Resume under the declared recipe: the rule must be the one the file was written by (a reference-recipe file
+// counts as "adam"); its state slabs, step count, EMA and progress are restored.  A file without an average
+// (or a run without one) restarts the average from the loaded weights.  The hyper-parameters the file records
+// (betas, eps, weight_decay, momentum, the EMA decay) are a record only: like the learning rate, the resuming
+// run's config decides them, so a run may be continued with, say, another weight decay.
+inline void load_training_state(const std::string& path, BaselineUNetImpl& m, optim::Optimizer& opt, RecipeProgress& progress) {
+    std::ifstream f = load_checkpoint_tensors(path, m);
+    const RecipeSections s = read_recipe_sections(f, path);
+    const int mine = opt.rule(), theirs = s.have_rule ? s.rule : CAD_OPTIM_ADAM;
+    if ((s.have_rule || s.reference_adam) && theirs != mine)
+        throw std::runtime_error("checkpoint " + path + " was written by optimizer '" + optim::Optimizer::rule_name(theirs) +
+                                 (s.reference_adam ? "' (reference recipe)" : "'") + " but this run declares '" +
+                                 optim::Optimizer::rule_name(mine) + "'");
+    float *mp = nullptr, *vp = nullptr, *ep = nullptr;
+    cad::check(cad_optim_state(opt.handle(), &mp, &vp, &ep), "optim_state");
+    int64_t nflat = 0;
+    cad::check(cad_unet_flat(m.handle(), nullptr, nullptr, &nflat), "flat");
+    if (!s.slabs.empty()) {
+        if (s.nflat != nflat || (int)s.slabs.size() != (vp ? 2 : 1))
+            throw std::runtime_error("optimizer state size mismatch in " + path);
+        cad::check(cad_memcpy(mp, s.slabs[0].data(), 4 * nflat, 0, nullptr), "h2d");
+        if (vp) cad::check(cad_memcpy(vp, s.slabs[1].data(), 4 * nflat, 0, nullptr), "h2d");
+        opt.set_step_count(s.step);
+    }
+    if (ep) {
+        if ((int64_t)s.ema.size() == nflat) cad::check(cad_memcpy(ep, s.ema.data(), 4 * nflat, 0, nullptr), "h2d");
+        else opt.attach_ema(opt.options().ema_decay);
+    }
+    if (s.have_progress) progress = s.progress;
 }
 
 class TensorBoardTrainerEnhanced {
@@ -389,11 +576,88 @@ public:
         bool tensorboard = true;     // event files under <tensorboard_dir>/<experiment_name> + <log_dir>/tensorboard_scalars.csv
         bool save_optimizer = true;  // also write <name>_epoch_N.cadckpt next to each .pt
         int64_t bucket_elems = 25 << 18;   // data-parallel gradient buckets (25 MB)
+        // The declared recipe (TrainingConfig, trainer.h:24-92; the epoch loop :262-316).  Off by default: the
+        // trainers then run the reference's Adam at a constant rate and ignore every field below.
+        bool recipe_declared = false;
+        std::string optimizer = "adam";      // adam | adamw | sgd
+        std::string lr_scheduler = "none";   // none | step | cosine (cad_lr_at)
+        int lr_step_size = 30;
+        float lr_gamma = 0.1f;
+        int lr_warmup_epochs = 0;
+        float lr_min = 0.f;
+        float momentum = 0.9f;               // SGD
+        float adam_betas[2] = {0.9f, 0.999f};
+        float adam_eps = 1e-8f;
+        bool use_early_stopping = false;
+        int early_stop_patience = 20;        // validations without improvement
+        float early_stop_min_delta = 0.f;
+        std::string metric_to_monitor = "abs_rel";   // abs_rel sq_rel rmse rmse_log a1|delta_1.25 a2 a3 loss
+        bool metric_lower_is_better = true;
+        bool save_best_only = false;         // no periodic checkpoints (best_model.* and final_model.* only)
+        int keep_last_n_checkpoints = 0;     // newest epoch checkpoints kept; 0 keeps all
+        float ema_decay = 0.f;               // > 0: exponential moving average of the weights (U-Net family)
     };
+
+    // ---- the declared recipe's pieces shared with GeometryTrainer ----
+    static cad_optim_opts optimOptions(const Config& c) {
+        return cad_optim_opts{optim::Optimizer::rule_of(c.optimizer), c.learning_rate, c.adam_betas[0], c.adam_betas[1],
+                              c.adam_eps, c.weight_decay, c.momentum, c.ema_decay};
+    }
+    // the rate of 1-based `epoch` (cad_lr_at); throws for plateau / unknown schedulers, naming the value
+    static float learningRateAt(const Config& c, int epoch) {
+        cad_lr_opts o{c.learning_rate, c.lr_scheduler.c_str(), c.lr_step_size, c.lr_gamma, c.lr_warmup_epochs, c.lr_min};
+        float lr = 0.f;
+        cad::check(cad_lr_at(&o, epoch - 1, c.num_epochs, &lr), "optimization");
+        return lr;
+    }
+    // start-up checks of a declared recipe (before any training work)
+    static void checkRecipe(const Config& c, bool data_parallel) {
+        if (!c.recipe_declared) return;
+        optim::Optimizer::rule_of(c.optimizer);
+        learningRateAt(c, 1);
+        static const char* const known[] = {"abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "delta_1.25", "a2", "a3", "loss"};
+        if (std::find(std::begin(known), std::end(known), c.metric_to_monitor) == std::end(known))
+            throw std::runtime_error("validation.primary_metric '" + c.metric_to_monitor + "': expected abs_rel, sq_rel, "
+                                     "rmse, rmse_log, a1 (delta_1.25), a2, a3 or loss");
+        if (c.ema_decay < 0.f || c.ema_decay >= 1.f) throw std::runtime_error("ema.decay must be in [0, 1)");
+        if (c.use_early_stopping && data_parallel)
+            throw std::runtime_error("early stopping with hardware.distributed: true needs a stop coordinated across "
+                                     "ranks, which is not built: turn one of them off");
+    }
+    // keeps the keep_last_n highest epochs that have <experiment>_epoch_N.* files (.pt, .cadckpt, _ema.pt) and
+    // deletes the files of every other epoch, whatever save_interval spaced them by; never best_* / final_*
+    static void pruneCheckpoints(const Config& c) {
+        if (c.keep_last_n_checkpoints <= 0) return;
+        const std::string prefix = c.experiment_name + "_epoch_";
+        std::error_code ec;
+        std::vector<std::pair<long, std::filesystem::path>> files;   // (epoch, file)
+        std::vector<long> epochs;
+        for (auto& e : std::filesystem::directory_iterator(c.checkpoint_dir, ec)) {
+            const std::string name = e.path().filename().string();
+            if (name.compare(0, prefix.size(), prefix) != 0) continue;
+            char* end = nullptr;
+            const long n = std::strtol(name.c_str() + prefix.size(), &end, 10);
+            if (end == name.c_str() + prefix.size() || (*end != '.' && *end != '_')) continue;
+            files.emplace_back(n, e.path());
+            epochs.push_back(n);
+        }
+        std::sort(epochs.begin(), epochs.end());
+        epochs.erase(std::unique(epochs.begin(), epochs.end()), epochs.end());
+        if ((int)epochs.size() <= c.keep_last_n_checkpoints) return;
+        const long oldest_kept = epochs[epochs.size() - (size_t)c.keep_last_n_checkpoints];
+        for (auto& f : files)
+            if (f.first < oldest_kept) std::filesystem::remove(f.second, ec);
+    }
 
     struct ValidationMetrics {   // enhanced.h:65-74
         float loss = 0.0f, abs_rel = 0.0f, sq_rel = 0.0f, rmse = 0.0f, rmse_log = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
     };
+    // val_metrics[config_.metric_to_monitor] (trainer.h:281)
+    static float monitoredMetric(const Config& c, const ValidationMetrics& v) {
+        const std::string& k = c.metric_to_monitor;
+        return k == "loss" ? v.loss : k == "sq_rel" ? v.sq_rel : k == "rmse" ? v.rmse : k == "rmse_log" ? v.rmse_log
+             : (k == "a1" || k == "delta_1.25") ? v.a1 : k == "a2" ? v.a2 : k == "a3" ? v.a3 : v.abs_rel;
+    }
     // the validation scalars of an epoch (:196-208), in the reference's order; shared with GeometryTrainer
     template <class Scalar>
     static void validationScalars(Scalar&& scalar, const ValidationMetrics& v) {
@@ -415,7 +679,14 @@ public:
         if (!model_ || !loss_fn_) throw std::runtime_error("TensorBoardTrainerEnhanced: model and loss are required");
         rank_ = comm_ ? comm_->rank() : 0;
         world_ = comm_ ? comm_->size() : 1;
-        optimizer_ = std::make_shared<optim::Adam>(*model_, config_.learning_rate, config_.weight_decay);
+        lr_ = config_.learning_rate;
+        checkRecipe(config_, comm_ != nullptr);
+        if (config_.recipe_declared) {
+            recipe_ = std::make_shared<optim::Optimizer>(*model_, optimOptions(config_));
+            progress_.best_metric = config_.metric_lower_is_better ? INFINITY : -INFINITY;
+        } else {
+            optimizer_ = std::make_shared<optim::Adam>(*model_, config_.learning_rate, config_.weight_decay);
+        }
         if (lead()) {
             std::filesystem::create_directories(config_.checkpoint_dir);
             std::filesystem::create_directories(config_.log_dir);
@@ -431,19 +702,34 @@ public:
             }
         }
         if (comm_) comm_->broadcast_parameters(*model_, 0);   // identical replicas
+        if (comm_ && ema()) recipe_->attach_ema(config_.ema_decay);   // the average starts from the broadcast weights
     }
     const EventWriter* events() const { return events_.get(); }
 
-    optim::Adam& optimizer() { return *optimizer_; }
+    // the reference recipe's Adam (a declared recipe has recipe_optimizer() instead)
+    optim::Adam& optimizer() {
+        if (!optimizer_) throw std::runtime_error("optimizer(): the declared recipe runs recipe_optimizer()");
+        return *optimizer_;
+    }
+    optim::Optimizer* recipe_optimizer() { return recipe_.get(); }
+    int64_t optimizer_step_count() const { return recipe_ ? recipe_->step_count() : optimizer_->step_count(); }
+    const RecipeProgress& progress() const { return progress_; }
     int64_t global_step() const { return global_step_; }
-    // resume: parameters, BN buffers and the Adam state (.cadckpt), or the weights of a torch::save
-    // archive (.pt: ours or the reference's; the optimizer starts fresh)
+    // resume: parameters, BN buffers and the optimizer state (.cadckpt; with a declared recipe also the EMA and
+    // the best-metric bookkeeping), or the weights of a torch::save archive (.pt: ours or the reference's; the
+    // optimizer and the average start fresh)
     void loadCheckpoint(const std::string& path) {
-        if (path.size() >= 3 && path.compare(path.size() - 3, 3, ".pt") == 0) load(*model_, path);
+        const bool pt = path.size() >= 3 && path.compare(path.size() - 3, 3, ".pt") == 0;
+        if (pt) load(*model_, path);
+        else if (recipe_) load_training_state(path, *model_, *recipe_, progress_);
         else load_training_state(path, *model_, *optimizer_);
         if (comm_) comm_->broadcast_parameters(*model_, 0);
+        if (pt && ema()) recipe_->attach_ema(config_.ema_decay);
     }
-    void saveTrainingState(const std::string& path) { save_training_state(path, *model_, *optimizer_); }
+    void saveTrainingState(const std::string& path) {
+        if (recipe_) save_training_state(path, *model_, *recipe_, progress_);
+        else save_training_state(path, *model_, *optimizer_);
+    }
 
     // enhanced.h:142-240.  Epochs continue after a resumed optimizer step count (whole epochs done).
     void train(std::shared_ptr<SunRGBDLoader> train_loader, std::shared_ptr<SunRGBDLoader> val_loader = nullptr) {
@@ -469,29 +755,49 @@ public:
             events_->flush();
         }
         const auto t0 = std::chrono::steady_clock::now();
-        global_step_ = optimizer_->step_count() / nb * nb;
-        for (int epoch = 1 + (int)(optimizer_->step_count() / nb); epoch <= config_.num_epochs; ++epoch) {
+        global_step_ = optimizer_step_count() / nb * nb;
+        bool stop = false;
+        for (int epoch = 1 + (int)(optimizer_step_count() / nb); epoch <= config_.num_epochs && !stop; ++epoch) {
             const auto te = std::chrono::steady_clock::now();
             if (lead()) std::cout << "\n" << std::string(60, '=') << "\nEpoch " << epoch << "/" << config_.num_epochs << "\n";
+            if (recipe_) {   // warmup / scheduler (trainer.h:266-269, :305-308): the epoch's rate, a function of the epoch
+                lr_ = learningRateAt(config_, epoch);
+                recipe_->set_lr(lr_);
+            }
             const float train_loss = trainEpoch(*train_loader, nb, (int)global_step_, epoch);
             if (lead()) {
                 scalar("loss/train", train_loss, epoch);
-                scalar("training/learning_rate", config_.learning_rate, epoch);
+                scalar("training/learning_rate", lr_, epoch);
                 logLossComponents(*train_loader, epoch);
                 scalar("training/epoch_time_seconds",
                        (double)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - te).count(),
                        epoch);
             }
             ValidationMetrics vm;
+            bool best = false;   // this epoch's validation improved: best_model.* holds this epoch's checkpoint
             if (lead() && val_loader && config_.val_interval > 0 && epoch % config_.val_interval == 0) {
+                if (ema()) recipe_->ema_swap();   // the averaged weights are what is validated and monitored
                 vm = validateEpoch(*val_loader, epoch);
+                if (ema()) recipe_->ema_swap();
                 validationScalars([&](const char* tag, double v) { scalar(tag, v, epoch); }, vm);
+                if (recipe_) {   // trainer.h:280-301
+                    best = progress_.improved(monitoredMetric(config_, vm), config_.metric_lower_is_better,
+                                              config_.early_stop_min_delta);
+                    if (config_.use_early_stopping && progress_.epochs_without_improvement >= config_.early_stop_patience) {
+                        logMessage("Early stopping triggered after " + std::to_string(epoch) + " epochs");
+                        stop = true;   // the epoch's records are still written; final_model.* follows
+                    }
+                }
             }
             if (lead() && config_.histogram_interval > 0 && epoch % config_.histogram_interval == 0)
                 logGradientStatistics(epoch);
             if (lead() && events_ && config_.viz_interval > 0 && epoch % config_.viz_interval == 0)
                 visualizeResults(*train_loader, epoch);
-            if (lead() && config_.save_interval > 0 && epoch % config_.save_interval == 0) saveCheckpoint(epoch);
+            const bool due = lead() && config_.save_interval > 0 && epoch % config_.save_interval == 0 &&
+                             !(recipe_ && config_.save_best_only);   // trainer.h:311
+            if (due) saveCheckpoint(epoch);
+            if (best) saveBestModel(epoch, due);
+            if (due && recipe_) pruneCheckpoints(config_);
             const long total = (long)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count();
             if (lead()) {
                 logEpochMetrics(epoch, (int)global_step_, train_loss, vm, total);
@@ -501,8 +807,7 @@ public:
             global_step_ += nb;   // :233
         }
         if (lead()) {
-            save(*model_, config_.checkpoint_dir + "/final_model.pt");   // production_trainer.h:323-330
-            if (config_.save_optimizer) saveTrainingState(config_.checkpoint_dir + "/final_model.cadckpt");
+            saveModel(config_.checkpoint_dir + "/final_model");   // production_trainer.h:323-330
             logMessage("=== Training Complete ===");
         }
         events_.reset();   // closed at the end of train() (and by the destructor)
@@ -517,6 +822,7 @@ public:
 
 private:
     bool lead() const { return rank_ == 0; }
+    bool ema() const { return recipe_ && recipe_->has_ema(); }
     bool conditioned() const { return cad_unet_model(model_->handle()) != CAD_MODEL_BASELINE; }
 
     void ensure_buffers(const SunRGBDLoader& L) {
@@ -567,8 +873,7 @@ private:
             const int64_t first = (int64_t)bi * B * world_ + (int64_t)rank_ * B;
             const int bs = (int)std::min<int64_t>(B, n - first);
             next(ring, bs);
-            optimizer_->zero_grad();
-            forward();
+            forward();   // (zero_grad: every backward overwrites the gradient slab)
             DeviceTensor l = loss_fn_->forwardWithIntrinsics(pred_, gt_, rgb_, K_);
             if (comm_) comm_->backward_allreduce(*model_, loss_fn_->dpred(), config_.bucket_elems);
             else model_->backward(loss_fn_->dpred());
@@ -576,7 +881,8 @@ private:
             double gnorm = 0.0;
             if (config_.use_grad_clip) gnorm = clip_grad_norm_(*model_, config_.grad_clip_value, nullptr, 1.0 / world_);
             else cad::check(cad_clip_grad_norm(model_->handle(), INFINITY, 1.f / world_, nullptr), "prescale");
-            optimizer_->step();
+            if (recipe_) recipe_->step();
+            else optimizer_->step();
             if (comm_) comm_->allreduce(l.data, 5);   // the logged loss: mean over replicas
             const float lv = l.to_host()[0] / world_;   // loss.item<float>() (:307)
             if (!std::isfinite(lv)) throw std::runtime_error("non-finite loss at step " + std::to_string(global_step + bi));
@@ -587,9 +893,12 @@ private:
                 if (!config_.use_grad_clip) gnorm = clip_grad_norm_(*model_, INFINITY);   // computeGradientNorm
                 scalar("training/gradient_norm", gnorm, global_step + bi);
             }
-            if (lead() && ((bi + 1) % std::max(1, config_.log_interval) == 0 || bi == nb - 1))
+            if (lead() && ((bi + 1) % std::max(1, config_.log_interval) == 0 || bi == nb - 1)) {
                 std::cout << "\r  [" << std::setw(3) << (100 * (bi + 1) / nb) << "%] Batch " << (bi + 1) << "/" << nb
-                          << " | Loss: " << std::fixed << std::setprecision(4) << lv << std::flush;
+                          << " | Loss: " << std::fixed << std::setprecision(4) << lv;
+                if (recipe_) std::cout << " | LR: " << float_text(lr_);
+                std::cout << std::flush;
+            }
         }
         if (lead()) std::cout << std::endl;
         return (float)(total / std::max<int64_t>(1, seen));
@@ -657,8 +966,10 @@ private:
     void visualizeResults(SunRGBDLoader& L, int epoch) {
         ensure_buffers(L);
         model_->eval();
+        if (ema()) recipe_->ema_swap();   // the panels show the averaged model, as validation scores it
         PanelLogger::run(panels_, *events_, L, config_.device, config_.num_viz_samples, epoch, rgb_.data, gt_.data,
                          [&](cad_loader* ring) { next(ring, 1); }, [&] { forward(); return (const float*)pred_.data; });
+        if (ema()) recipe_->ema_swap();
         model_->train();
     }
 
@@ -671,16 +982,44 @@ private:
         ss << " | Time: " << elapsed << "s";
         logMessage(ss.str());
         metrics_csv_ << epoch << "," << step << "," << train_loss << "," << v.loss << "," << v.abs_rel << "," << v.sq_rel
-                     << "," << v.rmse << "," << v.rmse_log << "," << v.a1 << "," << v.a2 << "," << v.a3 << ","
-                     << config_.learning_rate << "," << elapsed << "\n";
+                     << "," << v.rmse << "," << v.rmse_log << "," << v.a1 << "," << v.a2 << "," << v.a3 << ",";
+        if (recipe_) metrics_csv_ << float_text(lr_);   // the epoch's scheduled rate, digits that read back exactly
+        else metrics_csv_ << config_.learning_rate;
+        metrics_csv_ << "," << elapsed << "\n";
         metrics_csv_.flush();
     }
 
+    std::string checkpointStem(int epoch) const {
+        return config_.checkpoint_dir + "/" + config_.experiment_name + "_epoch_" + std::to_string(epoch);
+    }
     void saveCheckpoint(int epoch) {   // :656-662: torch::save(model_, <dir>/<experiment>_epoch_N.pt)
-        const std::string stem = config_.checkpoint_dir + "/" + config_.experiment_name + "_epoch_" + std::to_string(epoch);
+        saveModel(checkpointStem(epoch));
+        logMessage("Checkpoint saved: " + checkpointStem(epoch) + ".pt");
+    }
+    // best_model.*: copies of this epoch's checkpoint files when one was just written (the same files byte for
+    // byte), else written on their own.  Only the files this run writes; a sibling an earlier run left is removed.
+    void saveBestModel(int epoch, bool checkpoint_written) {
+        namespace fs = std::filesystem;
+        const std::string best = config_.checkpoint_dir + "/best_model";
+        if (!checkpoint_written) saveModel(best);
+        const std::pair<const char*, bool> files[] = {{".pt", true}, {".cadckpt", config_.save_optimizer}, {"_ema.pt", ema()}};
+        for (const auto& [suffix, written] : files) {
+            if (!written) fs::remove(best + suffix);
+            else if (checkpoint_written) fs::copy_file(checkpointStem(epoch) + suffix, best + suffix, fs::copy_options::overwrite_existing);
+        }
+        logMessage("Best model saved: " + best + ".pt (epoch " + std::to_string(epoch) + ", " + config_.metric_to_monitor +
+                   " " + std::to_string(progress_.best_metric) + ")");
+    }
+    // <stem>.pt (the raw weights), <stem>.cadckpt (save_optimizer) and, with an EMA, <stem>_ema.pt: the averaged
+    // weights with the live BatchNorm buffers, an archive build/evaluate and build/predict load like any other
+    void saveModel(const std::string& stem) {
         save(*model_, stem + ".pt");
         if (config_.save_optimizer) saveTrainingState(stem + ".cadckpt");
-        logMessage("Checkpoint saved: " + stem + ".pt");
+        if (ema()) {
+            recipe_->ema_swap();
+            save(*model_, stem + "_ema.pt");
+            recipe_->ema_swap();
+        }
     }
 
     void scalar(const std::string& tag, double v, int64_t step) {
@@ -701,7 +1040,10 @@ private:
 
     std::shared_ptr<BaselineUNetImpl> model_;
     std::shared_ptr<CombinedDepthLoss> loss_fn_;
-    std::shared_ptr<optim::Adam> optimizer_;
+    std::shared_ptr<optim::Adam> optimizer_;       // the reference recipe
+    std::shared_ptr<optim::Optimizer> recipe_;     // the declared recipe (exactly one of the two exists)
+    RecipeProgress progress_;
+    float lr_ = 0.f;                               // the rate in force: config.learning_rate, or the epoch's schedule
     Config config_;
     std::shared_ptr<distributed::Communicator> comm_;
     int rank_ = 0, world_ = 1;
@@ -724,6 +1066,12 @@ public:
                     const Config& config)
         : model_(std::move(model)), loss_fn_(std::move(loss_fn)), config_(config) {
         if (!model_ || !loss_fn_) throw std::runtime_error("GeometryTrainer: model and loss are required");
+        TensorBoardTrainerEnhanced::checkRecipe(config_, false);
+        if (config_.recipe_declared && config_.ema_decay != 0.f)
+            throw std::runtime_error("ema: the weight average is built for the U-Net family only; turn ema off for "
+                                     "the geometry-aware networks");
+        lr_ = config_.learning_rate;
+        progress_.best_metric = config_.metric_lower_is_better ? INFINITY : -INFINITY;
         std::filesystem::create_directories(config_.checkpoint_dir);
         std::filesystem::create_directories(config_.log_dir);
         log_.open(config_.log_dir + "/training.log", std::ios::app);
@@ -749,29 +1097,45 @@ public:
         }
         const auto t0 = std::chrono::steady_clock::now();
         int64_t step = 0;
-        for (int epoch = 1; epoch <= config_.num_epochs; ++epoch) {
+        const bool declared = config_.recipe_declared;
+        bool stop = false;
+        for (int epoch = 1; epoch <= config_.num_epochs && !stop; ++epoch) {
             std::cout << "\n" << std::string(60, '=') << "\nEpoch " << epoch << "/" << config_.num_epochs << "\n";
+            if (declared) lr_ = TensorBoardTrainerEnhanced::learningRateAt(config_, epoch);
             const float tl = trainEpoch(*train_loader, nb, step);
             TensorBoardTrainerEnhanced::ValidationMetrics vm;
             scalar("loss/train", tl, epoch);
-            scalar("training/learning_rate", config_.learning_rate, epoch);
+            scalar("training/learning_rate", lr_, epoch);
             if (val_loader && config_.val_interval > 0 && epoch % config_.val_interval == 0) {
                 vm = validate(*val_loader);
                 TensorBoardTrainerEnhanced::validationScalars([&](const char* tag, double v) { scalar(tag, v, epoch); }, vm);
+                if (declared) {   // trainer.h:280-301, as TensorBoardTrainerEnhanced::train
+                    if (progress_.improved(TensorBoardTrainerEnhanced::monitoredMetric(config_, vm),
+                                           config_.metric_lower_is_better, config_.early_stop_min_delta))
+                        save(config_.checkpoint_dir + "/best_model.cadckpt");
+                    if (config_.use_early_stopping && progress_.epochs_without_improvement >= config_.early_stop_patience) {
+                        msg("Early stopping triggered after " + std::to_string(epoch) + " epochs");
+                        stop = true;
+                    }
+                }
             }
             if (config_.histogram_interval > 0 && epoch % config_.histogram_interval == 0) logGradientStatistics(epoch);
             if (events_ && config_.viz_interval > 0 && epoch % config_.viz_interval == 0) visualize(*train_loader, epoch);
-            if (config_.save_interval > 0 && epoch % config_.save_interval == 0)
+            if (config_.save_interval > 0 && epoch % config_.save_interval == 0 && !(declared && config_.save_best_only)) {
                 save(config_.checkpoint_dir + "/" + config_.experiment_name + "_epoch_" + std::to_string(epoch) +
                      ".cadckpt");
+                if (declared) TensorBoardTrainerEnhanced::pruneCheckpoints(config_);
+            }
             const long el = (long)std::chrono::duration_cast<std::chrono::seconds>(std::chrono::steady_clock::now() - t0).count();
             std::stringstream ss;
             ss << "Epoch " << epoch << " | Train Loss: " << std::fixed << std::setprecision(4) << tl;
             if (vm.loss > 0) ss << " | Val Loss: " << vm.loss << " | abs_rel: " << vm.abs_rel << " | rmse: " << vm.rmse;
             msg(ss.str());
             metrics_csv_ << epoch << "," << step << "," << tl << "," << vm.loss << "," << vm.abs_rel << "," << vm.sq_rel
-                         << "," << vm.rmse << "," << vm.rmse_log << "," << vm.a1 << "," << vm.a2 << "," << vm.a3 << ","
-                         << config_.learning_rate << "," << el << "\n";
+                         << "," << vm.rmse << "," << vm.rmse_log << "," << vm.a1 << "," << vm.a2 << "," << vm.a3 << ",";
+            if (declared) metrics_csv_ << float_text(lr_);
+            else metrics_csv_ << config_.learning_rate;
+            metrics_csv_ << "," << el << "\n";
             metrics_csv_.flush();
             scalar("training/total_time_seconds", (double)el, epoch);
             if (events_) events_->flush();
@@ -786,20 +1150,7 @@ public:
     void save(const std::string& path) {
         std::ofstream f(path, std::ios::binary);
         if (!f) throw std::runtime_error("cannot write checkpoint " + path);
-        auto ts = model_->named_parameters();
-        auto bs = model_->named_buffers();
-        ts.insert(ts.end(), bs.begin(), bs.end());
-        f.write("CADCKPT1", 8);
-        const int32_t n = (int32_t)ts.size();
-        f.write((const char*)&n, 4);
-        for (auto& t : ts) {
-            const int32_t ln = (int32_t)t.name.size(), nd = (int32_t)t.shape.size();
-            f.write((const char*)&ln, 4);
-            f.write(t.name.data(), ln);
-            f.write((const char*)&nd, 4);
-            f.write((const char*)t.shape.data(), 8 * nd);
-            f.write((const char*)t.value.data(), 4 * (int64_t)t.value.size());
-        }
+        write_checkpoint_tensors(f, *model_);
         msg("Checkpoint saved: " + path);
     }
 
@@ -835,7 +1186,13 @@ private:
             DeviceTensor l = loss_fn_->forwardWithIntrinsics(pred, gt_, rgb_, K_);
             model_->backward(loss_fn_->dpred());
             model_->clip_grad_norm_(config_.use_grad_clip ? config_.grad_clip_value : INFINITY);
-            model_->adam_step(config_.learning_rate, config_.weight_decay);
+            if (config_.recipe_declared) {
+                cad_optim_opts o = TensorBoardTrainerEnhanced::optimOptions(config_);
+                o.lr = lr_;
+                model_->optim_step(o);
+            } else {
+                model_->adam_step(config_.learning_rate, config_.weight_decay);
+            }
             const float lv = l.to_host()[0];
             if (!std::isfinite(lv)) throw std::runtime_error("non-finite loss at step " + std::to_string(step0 + bi));
             total += (double)lv * n;
@@ -908,6 +1265,8 @@ private:
     std::shared_ptr<GeometryAwareNetworkImpl> model_;
     std::shared_ptr<CombinedDepthLoss> loss_fn_;
     Config config_;
+    RecipeProgress progress_;   // the declared recipe's best metric / validations without improvement
+    float lr_ = 0.f;            // the rate in force: config.learning_rate, or the epoch's schedule
     std::ofstream log_, metrics_csv_;
     std::unique_ptr<EventWriter> events_;   // config.tensorboard only
     std::unique_ptr<PanelLogger> panels_;
