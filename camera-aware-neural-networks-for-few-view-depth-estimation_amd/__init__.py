@@ -16,7 +16,7 @@ def __getattr__(name):
     if name in ("BaselineUNet", "IntrinsicsConditionedUNet", "IntrinsicsAttentionUNet", "RayConditionedUNet", "CombinedDepthLoss", "Adam",
                 "Trainer", "Communicator", "save", "load", "clip_grad_norm_", "depth_metrics", "ray_directions", "camera_from_K",
                 "ResNetUNet", "GeometryAwareNetwork", "LightweightGeometryNetwork", "depth_metrics_full", "Evaluator",
-                "evaluate", "EVAL_KEYS", "valid_medians", "Optimizer"):
+                "evaluate", "EVAL_KEYS", "valid_medians", "Optimizer", "eval_strata_finish", "strata_angle_thresholds"):
         from . import model
         return getattr(model, name)
     if name == "lr_at":

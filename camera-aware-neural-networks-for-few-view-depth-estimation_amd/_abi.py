@@ -92,6 +92,37 @@ class EvalSummary(C.Structure):
     _fields_ = [("count", I64)] + [(k, F * 12) for k in ("mean", "std", "median", "min", "max", "pooled")]
 
 
+STRATA_MAX_BINS = 16                    # CAD_STRATA_MAX_BINS
+STRATA_AXES = {"depth": 0, "angle": 1}  # CAD_STRATA_DEPTH / CAD_STRATA_ANGLE
+
+
+class StrataConfig(C.Structure):
+    """cad_strata_config (cad.h): the depth cuts in metres and the angle cuts in degrees; 0 cuts: axis off."""
+    _fields_ = [("n_depth_cuts", I), ("depth_cuts", F * (STRATA_MAX_BINS - 1)), ("n_angle_cuts", I),
+                ("angle_cuts_deg", F * (STRATA_MAX_BINS - 1))]
+
+
+def strata_config(depth_bins=None, angle_bins=None) -> "StrataConfig":
+    """cad_strata_config of two cut lists (None or empty: that axis is off).  Only what the fixed-size struct
+    cannot hold is refused here (ValueError naming the count); every other rule is the library's."""
+    cfg = StrataConfig()
+    for name, cuts, n_field, field in (("depth_bins", depth_bins, "n_depth_cuts", "depth_cuts"),
+                                       ("angle_bins", angle_bins, "n_angle_cuts", "angle_cuts_deg")):
+        cuts = [] if cuts is None else [float(c) for c in cuts]
+        if len(cuts) > STRATA_MAX_BINS - 1:
+            raise ValueError(f"{name}: {len(cuts)} cuts given, at most {STRATA_MAX_BINS - 1} ({STRATA_MAX_BINS} bins)")
+        setattr(cfg, n_field, len(cuts))
+        for j, c in enumerate(cuts):
+            getattr(cfg, field)[j] = c
+    return cfg
+
+
+def strata_axis(axis) -> int:
+    if axis not in STRATA_AXES:
+        raise ValueError(f"axis must be one of {tuple(STRATA_AXES)}, not {axis!r}")
+    return STRATA_AXES[axis]
+
+
 COLORMAPS = {"gray": 0, "jet": 1, "hot": 2}   # CAD_CMAP_*; 3 = CAD_CMAP_CUSTOM (cad_exporter_set_lut)
 CMAP_CUSTOM = 3
 
@@ -234,6 +265,12 @@ SIGNATURES = {
     "cad_evaluator_sums": (I, [P, C.POINTER(C.c_double), P]),
     "cad_evaluator_metrics": (I, [P, FP, C.POINTER(EvalSummary)]),
     "cad_eval_finish": (I, [C.POINTER(C.c_double), I64, FP, C.POINTER(EvalSummary)]),
+    "cad_evaluator_set_strata": (I, [P, C.POINTER(StrataConfig)]),
+    "cad_evaluator_update_k": (I, [P, P, P, P, P, I, P]),
+    "cad_evaluator_strata_bins": (I, [P, I]),
+    "cad_evaluator_strata_sums": (I, [P, I, C.POINTER(C.c_double), P]),
+    "cad_strata_angle_thresholds": (I, [FP, I, FP]),
+    "cad_eval_strata_finish": (I, [C.POINTER(C.c_double), I64, I, FP, C.POINTER(EvalSummary)]),
     "cad_evaluator_set_alignment": (I, [P, I]),
     "cad_evaluator_get_alignment": (I, [P]),
     "cad_evaluator_alignment": (I, [P, FP, P]),
@@ -297,6 +334,7 @@ SIGNATURES = {
     "cad_dataset_destroy": (None, [P]),
     "cad_dataset_size": (I64, [P]),
     "cad_dataset_image_dir": (C.c_char_p, [P, I64]),
+    "cad_dataset_sensor": (C.c_char_p, [P, I64]),
     "cad_dataset_read": (I, [P, I64, P, I64, P, I64, P]),
     "cad_loader_create": (I, [P, I, I, I, P, C.c_uint32, I, I, I, C.POINTER(P)]),
     "cad_loader_destroy": (None, [P]),

@@ -130,6 +130,13 @@ class SunRGBDDataset:
         d = self.lib.cad_dataset_image_dir(self.h, i)
         return d.decode() if d else None
 
+    def sensor(self, i):
+        """The sample's manifest sensor_type ("synthetic" for the synthetic dataset)."""
+        s = self.lib.cad_dataset_sensor(self.h, i)
+        if s is None:
+            raise IndexError(i)
+        return s.decode()
+
     def read(self, i):
         import numpy as np
         info = _abi.DecodedInfo()

@@ -5,7 +5,9 @@
 //   build/evaluate -c <final_model.pt | .cadckpt> -g <train_config.yaml> [-o results/eval] [--data-dir D]
 //                  [--split val|train] [--save-predictions] [--gpu 0] [--dry-run]
 //                  [--align none|median|log_mean|scale_shift]
+//                  [--depth-bins 1,2,3,5] [--angle-bins 10,20,30] [--by-sensor]
 //   build/evaluate --compare A/per_sample.csv B/per_sample.csv [--metric abs_rel] [--seed 42]
+//   build/evaluate --compare A/per_sample_strata.csv B/per_sample_strata.csv --stratum depth:2 [--metric abs_rel]
 //
 // The model (model.architecture, init_features, max_depth, variant, use_pcl, use_attention), the data
 // section and training.batch_size come from the training YAML, the keys build/train reads; the synthetic
@@ -17,8 +19,17 @@
 // (fp32, H x W).  --align scores scale * pred + shift with a per-sample scale (median ratio, log mean or
 // least squares, computed on the device; cad.h "scale-aligned evaluation"): per_sample.csv then gains the
 // trailing columns scale, shift, aligned (0 where a fallback applied) and report.txt names the mode;
-// pred_<index>.npy stays the raw prediction, and with none every file is as without the flag.  Any
+// pred_<index>.npy stays the raw prediction, and with none every file is as without the flag.
+// --depth-bins / --angle-bins (cuts in metres / in degrees off the optical axis; cad.h "stratified
+// evaluation") add strata_depth.csv / strata_angle.csv (one row per bin: stratum, lo, hi, num_samples = the
+// samples with a valid pixel in the bin, pixel_share, then summary.csv's metric columns), per_sample_strata.csv
+// (long form: index, axis, bin, the twelve metrics; rows without a valid pixel are left out) and a report
+// section per axis; --by-sensor adds strata_sensor.csv (the per-sample rows grouped by the manifest's
+// sensor_type) and a trailing sensor column in per_sample.csv.  Without these options every file is as before.
+// --compare with --stratum axis:bin pairs the samples present in that stratum in both long-form files.  Any
 // exception prints "Error: <what>" and exits 1, like build/train.
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
@@ -26,6 +37,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <map>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -42,13 +54,21 @@ using namespace cad_cli;
 
 namespace {
 
+std::string cut_str(float v) {
+    std::ostringstream o;
+    o << std::setprecision(7) << v;   // the shortest form that tells two fp32 cuts apart in practice (0.1, not 0.100000001)
+    return o.str();
+}
+
 struct Args {
     std::string checkpoint, config, output = "results/eval", data_dir, split = "val", metric = "abs_rel";
     Alignment align = Alignment::None;
     std::vector<std::string> compare;
     int gpu = 0;
     uint32_t seed = 42;
-    bool save_predictions = false, dry_run = false;
+    bool save_predictions = false, dry_run = false, by_sensor = false;
+    std::vector<float> depth_bins, angle_bins;   // cuts; empty: the option was not given
+    std::string stratum;                         // --compare: "depth:2"
 };
 
 void usage() {
@@ -63,10 +83,48 @@ void usage() {
                  "      --dry-run         Print the evaluation plan and exit; no GPU use\n"
                  "      --align arg       Per-sample scale alignment before the metrics: none, median,\n"
                  "                        log_mean or scale_shift (default: none)\n"
+                 "      --depth-bins arg  Ascending depth cuts in metres, e.g. 1,2,3,5: metrics per depth range\n"
+                 "      --angle-bins arg  Ascending cuts in degrees off the optical axis, e.g. 10,20,30\n"
+                 "      --by-sensor       Metrics per manifest sensor_type\n"
                  "      --compare A B     Paired comparison of two per_sample.csv files (no GPU use)\n"
+                 "      --stratum arg     With --compare on two per_sample_strata.csv files: axis:bin, e.g. depth:2\n"
                  "      --metric arg      Column compared by --compare (default: abs_rel)\n"
                  "      --seed arg        Bootstrap seed of --compare (default: 42)\n"
                  "  -h, --help            Print help\n";
+}
+
+// "1,2,3,5" -> cuts: at least one and at most 15 finite numbers, strictly ascending (the range is checked
+// once the config is read)
+std::vector<float> parse_cuts(const std::string& opt, const std::string& list) {
+    std::vector<float> out;
+    std::string cell;
+    std::stringstream ls(list);
+    while (std::getline(ls, cell, ',')) {
+        size_t used = 0;
+        float v = 0.f;
+        try {
+            v = std::stof(cell, &used);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+        if (cell.empty() || used != cell.size() || !std::isfinite(v))
+            throw std::runtime_error(opt + " '" + list + "': '" + cell + "' is not a number");
+        if (!out.empty() && !(out.back() < v))
+            throw std::runtime_error(opt + " '" + list + "': the cuts must be strictly ascending (" + cell + " follows " +
+                                     cut_str(out.back()) + ")");
+        out.push_back(v);
+    }
+    if (out.empty() || (!list.empty() && list.back() == ',')) throw std::runtime_error(opt + " '" + list + "': expected a list of cuts such as 1,2,3");
+    if (out.size() > (size_t)CAD_STRATA_MAX_BINS - 1)
+        throw std::runtime_error(opt + " '" + list + "': " + std::to_string(out.size()) + " cuts, at most " +
+                                 std::to_string(CAD_STRATA_MAX_BINS - 1));
+    return out;
+}
+void check_cut_range(const std::string& opt, const std::vector<float>& cuts, float lo, float hi, const char* unit) {
+    for (float v : cuts)
+        if (!(v > lo && v < hi))
+            throw std::runtime_error(opt + ": cut " + cut_str(v) + " is not strictly inside (" + cut_str(lo) + ", " + cut_str(hi) +
+                                     ") " + unit);
 }
 
 Args parse_args(int argc, char** argv) {
@@ -74,9 +132,10 @@ Args parse_args(int argc, char** argv) {
     for (int i = 1; i < argc; ++i) {
         std::string k = argv[i], v;
         auto eq = k.find('=');
-        if (k.rfind("--", 0) == 0 && eq != std::string::npos) { v = k.substr(eq + 1); k = k.substr(0, eq); }
+        const bool has_eq = k.rfind("--", 0) == 0 && eq != std::string::npos;
+        if (has_eq) { v = k.substr(eq + 1); k = k.substr(0, eq); }
         auto next = [&]() -> std::string {
-            if (!v.empty()) return v;
+            if (!v.empty() || (has_eq && (k == "--depth-bins" || k == "--angle-bins"))) return v;
             if (i + 1 >= argc) throw std::runtime_error("missing value for " + k);
             return argv[++i];
         };
@@ -93,7 +152,11 @@ Args parse_args(int argc, char** argv) {
             const std::string m = next();
             if (!parseAlignment(m, &a.align))
                 throw std::runtime_error("--align '" + m + "': expected none, median, log_mean or scale_shift");
-        } else if (k == "--metric") a.metric = next();
+        } else if (k == "--depth-bins") a.depth_bins = parse_cuts(k, next());
+        else if (k == "--angle-bins") a.angle_bins = parse_cuts(k, next());
+        else if (k == "--by-sensor") a.by_sensor = true;
+        else if (k == "--stratum") a.stratum = next();
+        else if (k == "--metric") a.metric = next();
         else if (k == "--seed") a.seed = (uint32_t)std::stoul(next());
         else if (k == "--compare") {
             a.compare.push_back(next());
@@ -133,7 +196,73 @@ Column read_column(const std::string& path, const std::string& metric) {
     return c;
 }
 
+// the rows of one stratum of a per_sample_strata.csv (index, axis, bin, metrics...)
+Column read_stratum_column(const std::string& path, const std::string& metric, const std::string& axis, long long bin) {
+    std::ifstream f(path);
+    if (!f) throw std::runtime_error("Cannot open " + path);
+    std::string line, cell;
+    if (!std::getline(f, line)) throw std::runtime_error(path + " is empty");
+    int col = -1, n = 0;
+    for (std::stringstream hs(line); std::getline(hs, cell, ','); ++n) {
+        static const char* head[3] = {"index", "axis", "bin"};
+        if (n < 3 && cell != head[n])
+            throw std::runtime_error(path + ": the first columns must be index,axis,bin (a per_sample_strata.csv file)");
+        if (n >= 3 && cell == metric) col = n;
+    }
+    if (col < 3) throw std::runtime_error(path + " has no column '" + metric + "'");
+    Column c;
+    while (std::getline(f, line)) {
+        if (line.empty()) continue;
+        std::vector<std::string> cells;
+        for (std::stringstream ls(line); std::getline(ls, cell, ',');) cells.push_back(cell);
+        if ((int)cells.size() <= col) throw std::runtime_error(path + ": short row '" + line + "'");
+        if (cells[1] != axis || std::stoll(cells[2]) != bin) continue;
+        c.index.push_back(std::stoll(cells[0]));
+        c.value.push_back(std::stod(cells[(size_t)col]));
+    }
+    return c;
+}
+
+int compare_stratum(const Args& a) {
+    const auto colon = a.stratum.find(':');
+    const std::string axis = a.stratum.substr(0, colon);
+    long long bin = -1;
+    size_t used = 0;
+    if (colon != std::string::npos) {
+        try {
+            bin = std::stoll(a.stratum.substr(colon + 1), &used);
+        } catch (const std::exception&) {
+            bin = -1;
+        }
+    }
+    if ((axis != "depth" && axis != "angle") || bin < 0 || bin >= CAD_STRATA_MAX_BINS || used != a.stratum.size() - colon - 1)
+        throw std::runtime_error("--stratum '" + a.stratum + "': expected depth:<bin> or angle:<bin>");
+    const Column x = read_stratum_column(a.compare[0], a.metric, axis, bin), y = read_stratum_column(a.compare[1], a.metric, axis, bin);
+    std::map<long long, double> ym;
+    for (size_t i = 0; i < y.index.size(); ++i) ym[y.index[i]] = y.value[i];
+    std::vector<double> xv, yv;
+    size_t only_x = 0;
+    for (size_t i = 0; i < x.index.size(); ++i) {
+        const auto it = ym.find(x.index[i]);
+        if (it == ym.end()) {
+            ++only_x;
+            continue;
+        }
+        xv.push_back(x.value[i]);
+        yv.push_back(it->second);
+    }
+    const size_t only_y = y.index.size() - xv.size();
+    if (only_x + only_y > 0)
+        throw std::runtime_error(std::to_string(only_x + only_y) + " samples are present in stratum " + a.stratum +
+                                 " of only one file (" + std::to_string(only_x) + " only in " + a.compare[0] + ", " +
+                                 std::to_string(only_y) + " only in " + a.compare[1] + "): a paired comparison needs the same samples");
+    if (xv.size() < 2) throw std::runtime_error("a paired comparison needs at least two samples in stratum " + a.stratum);
+    std::cout << eval_stats::compare_models(xv, yv, a.compare[0], a.compare[1], a.metric + " [" + a.stratum + "]", a.seed);
+    return 0;
+}
+
 int compare(const Args& a) {
+    if (!a.stratum.empty()) return compare_stratum(a);
     const Column x = read_column(a.compare[0], a.metric), y = read_column(a.compare[1], a.metric);
     if (x.index.size() != y.index.size())
         throw std::runtime_error("the files hold " + std::to_string(x.index.size()) + " and " +
@@ -145,6 +274,81 @@ int compare(const Args& a) {
 }
 
 // ---- outputs ----
+struct StratumRow {
+    std::string name, lo, hi;
+    cad_eval_summary s;
+    double pixels = 0.0;
+};
+
+// the sensor strata: the per-sample rows grouped by sensor (first appearance order), each group finished
+// like the whole table (a sample without a valid pixel counts as twelve zeros)
+std::vector<StratumRow> sensor_strata(const EvaluationResult& r) {
+    std::vector<std::string> names;
+    for (const auto& s : r.sensors)
+        if (std::find(names.begin(), names.end(), s) == names.end()) names.push_back(s);
+    std::vector<StratumRow> rows;
+    for (const auto& name : names) {
+        std::vector<double> sums;
+        StratumRow row;
+        row.name = name;
+        for (size_t i = 0; i < r.sensors.size(); ++i)
+            if (r.sensors[i] == name) {
+                sums.insert(sums.end(), r.sums.begin() + (long)(i * CAD_EVAL_METRICS), r.sums.begin() + (long)((i + 1) * CAD_EVAL_METRICS));
+                row.pixels += r.sums[i * CAD_EVAL_METRICS];
+            }
+        cad::check(cad_eval_finish(sums.data(), (int64_t)(sums.size() / CAD_EVAL_METRICS), nullptr, &row.s), "cad_eval_finish");
+        rows.push_back(row);
+    }
+    return rows;
+}
+
+std::vector<StratumRow> axis_strata(const StrataResult& st) {
+    std::vector<StratumRow> rows;
+    const size_t n = st.bins ? st.sums.size() / ((size_t)st.bins * CAD_EVAL_METRICS) : 0;
+    for (int b = 0; b < st.bins; ++b) {
+        StratumRow row;
+        row.name = std::to_string(b);
+        row.lo = cut_str(st.edges[(size_t)b]);
+        row.hi = cut_str(st.edges[(size_t)b + 1]);
+        row.s = st.summary[(size_t)b];
+        for (size_t i = 0; i < n; ++i) row.pixels += st.sums[(i * (size_t)st.bins + (size_t)b) * CAD_EVAL_METRICS];
+        rows.push_back(row);
+    }
+    return rows;
+}
+
+void write_strata_csv(const std::string& path, const std::vector<StratumRow>& rows, double total_pixels) {
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "stratum,lo,hi,num_samples,pixel_share";
+    for (const char* k : metricKeys())
+        for (const char* s : {"mean", "std", "median", "pooled"}) f << "," << k << "_" << s;
+    f << "\n" << std::setprecision(9);
+    for (const auto& row : rows) {
+        f << row.name << "," << row.lo << "," << row.hi << "," << row.s.count << ","
+          << (total_pixels > 0 ? row.pixels / total_pixels : 0.0);
+        for (int k = 0; k < CAD_EVAL_METRICS; ++k)
+            for (const float* m : {row.s.mean, row.s.std, row.s.median, row.s.pooled}) f << "," << m[k];
+        f << "\n";
+    }
+}
+
+void report_strata(std::ostream& rep, const std::string& rule, const char* title, const char* unit,
+                   const std::vector<StratumRow>& rows, double total_pixels) {
+    rep << rule << "\n" << title << "\n" << rule << "\n\n";
+    rep << std::fixed << std::setprecision(4);
+    for (const auto& row : rows) {
+        rep << "  " << row.name;
+        if (!row.lo.empty()) rep << " [" << row.lo << ", " << row.hi << ") " << unit;
+        rep << ": " << row.s.count << " samples, " << (total_pixels > 0 ? 100.0 * row.pixels / total_pixels : 0.0)
+            << "% of the valid pixels\n";
+        rep << "    AbsRel:   " << row.s.mean[0] << " ± " << row.s.std[0] << "\n";
+        rep << "    RMSE:     " << row.s.mean[2] << " ± " << row.s.std[2] << "\n";
+        rep << "    δ < 1.25: " << row.s.mean[6] << " ± " << row.s.std[6] << "\n";
+    }
+    rep << "\n";
+}
+
 void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
     const auto& keys = metricKeys();
     const bool al = a.align != Alignment::None;
@@ -154,11 +358,13 @@ void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
         f << "index";
         for (const char* k : keys) f << "," << k;
         if (al) f << ",scale,shift,aligned";
+        if (a.by_sensor) f << ",sensor";
         f << "\n" << std::setprecision(9);
         for (size_t i = 0; i < r.sample_results.size(); ++i) {
             f << i;
             for (int k = 0; k < CAD_EVAL_METRICS; ++k) f << "," << r.per_sample[i * CAD_EVAL_METRICS + (size_t)k];
             if (al) f << "," << r.alignment[2 * i] << "," << r.alignment[2 * i + 1] << "," << (int)r.aligned[i];
+            if (a.by_sensor) f << "," << r.sensors[i];
             f << "\n";
         }
     }
@@ -223,7 +429,41 @@ void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
     rep << "  RMSElog:  " << r.median_metrics.at("rmse_log") << "\n";
     rep << "  δ < 1.25: " << r.median_metrics.at("delta_1.25") << "\n\n";
     rep << rule << "\n              Pooled Over All Valid Pixels\n" << rule << "\n\n";
-    rep << formatMetrics(r.pooled_metrics) << "\n" << bar << "\n";
+    rep << formatMetrics(r.pooled_metrics) << "\n";
+    double total_pixels = 0.0;
+    for (size_t i = 0; i < r.sums.size(); i += CAD_EVAL_METRICS) total_pixels += r.sums[i];
+    if (r.depth_strata.bins) {
+        const auto rows = axis_strata(r.depth_strata);
+        write_strata_csv(a.output + "/strata_depth.csv", rows, total_pixels);
+        report_strata(rep, rule, "                  Metrics By Depth Range", "m", rows, total_pixels);
+    }
+    if (r.angle_strata.bins) {
+        const auto rows = axis_strata(r.angle_strata);
+        write_strata_csv(a.output + "/strata_angle.csv", rows, total_pixels);
+        report_strata(rep, rule, "           Metrics By Ray Angle Off The Optical Axis", "degrees", rows, total_pixels);
+    }
+    if (a.by_sensor) {
+        const auto rows = sensor_strata(r);
+        write_strata_csv(a.output + "/strata_sensor.csv", rows, total_pixels);
+        report_strata(rep, rule, "                     Metrics By Sensor", "", rows, total_pixels);
+    }
+    if (r.depth_strata.bins || r.angle_strata.bins) {
+        std::ofstream f(a.output + "/per_sample_strata.csv");
+        if (!f) throw std::runtime_error("cannot write " + a.output + "/per_sample_strata.csv");
+        f << "index,axis,bin";
+        for (const char* k : keys) f << "," << k;
+        f << "\n" << std::setprecision(9);
+        for (size_t i = 0; i < r.sample_results.size(); ++i)
+            for (const auto* st : {&r.depth_strata, &r.angle_strata})
+                for (int b = 0; b < st->bins; ++b) {
+                    const size_t at = (i * (size_t)st->bins + (size_t)b) * CAD_EVAL_METRICS;
+                    if (!(st->sums[at] > 0)) continue;
+                    f << i << "," << (st == &r.depth_strata ? "depth" : "angle") << "," << b;
+                    for (int k = 0; k < CAD_EVAL_METRICS; ++k) f << "," << st->per_sample[at + (size_t)k];
+                    f << "\n";
+                }
+    }
+    rep << bar << "\n";
 }
 
 int run(const Args& a) {
@@ -236,6 +476,8 @@ int run(const Args& a) {
         throw std::runtime_error("checkpoint '" + a.checkpoint + "': expected a .pt or .cadckpt file");
     Config c = load_config(yaml_lite::load_file(a.config));
     if (!a.data_dir.empty()) c.data_dir = a.data_dir;
+    check_cut_range("--depth-bins", a.depth_bins, EvaluationConfig().min_depth, c.max_depth, "metres");
+    check_cut_range("--angle-bins", a.angle_bins, 0.f, 90.f, "degrees");
     const bool geo = c.architecture == "geometry_aware";
     if (geo && pt) throw std::runtime_error("geometry_aware checkpoints are .cadckpt files");
     const bool real = c.dataset != "synthetic";
@@ -259,7 +501,17 @@ int run(const Args& a) {
                   << ", \"batches\": " << (ns + c.batch_size - 1) / c.batch_size << ", \"height\": " << c.height
                   << ", \"width\": " << c.width << ", \"device\": " << a.gpu << ", \"output\": \"" << a.output
                   << "\", \"save_predictions\": " << (a.save_predictions ? "true" : "false") << ", \"align\": \""
-                  << alignmentName(a.align) << "\"}" << std::endl;
+                  << alignmentName(a.align) << "\"";
+        const auto list = [](const char* key, const std::vector<float>& v) {
+            if (v.empty()) return;
+            std::cout << ", \"" << key << "\": [";
+            for (size_t j = 0; j < v.size(); ++j) std::cout << (j ? ", " : "") << cut_str(v[j]);
+            std::cout << "]";
+        };
+        list("depth_bins", a.depth_bins);
+        list("angle_bins", a.angle_bins);
+        if (a.by_sensor) std::cout << ", \"by_sensor\": true";
+        std::cout << "}" << std::endl;
         return 0;
     }
     int ndev = 0;
@@ -283,6 +535,9 @@ int run(const Args& a) {
     ec.device = a.gpu;
     ec.max_samples = ns;
     ec.align = a.align;
+    ec.depth_cuts = a.depth_bins;
+    ec.angle_cuts_deg = a.angle_bins;
+    ec.by_sensor = a.by_sensor;
     if (a.save_predictions)
         ec.on_batch = [&](int64_t first, const DeviceTensor& pred, int n) {
             const std::vector<float> h = pred.to_host();

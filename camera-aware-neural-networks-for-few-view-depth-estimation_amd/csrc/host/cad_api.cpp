@@ -2088,7 +2088,46 @@ struct cad_evaluator {
     float* align_table = nullptr;      // [capacity][2] {scale, shift}
     uint8_t* align_flags = nullptr;    // [capacity], 0 where a fallback applied
     cad::EvalAlignWs align_ws{};
+    // stratified evaluation (cad_evaluator_set_strata): one allocation per configuration
+    int W = 0;
+    cad::EvalStrata strata{};          // 0 cuts on both axes: off
+    int strata_alloc_bins = 0;         // total bins the allocation was made for
+    double* strata_table = nullptr;    // [capacity][nbt][12], depth bins first
+    double* strata_part = nullptr;     // [Bmax][nb][nbt][12]
 };
+
+namespace {
+int strata_axis_bins(const cad_evaluator* e, int axis) {
+    const int m = axis == CAD_STRATA_DEPTH ? e->strata.n_depth_cuts : e->strata.n_angle_cuts;
+    return m > 0 ? m + 1 : 0;
+}
+int strata_total_bins(const cad_evaluator* e) { return strata_axis_bins(e, CAD_STRATA_DEPTH) + strata_axis_bins(e, CAD_STRATA_ANGLE); }
+extern "C++" std::string fmt_float(double v) {
+    char buf[64];
+    std::snprintf(buf, sizeof(buf), "%.9g", v);
+    return buf;
+}
+// (float)(tan(deg pi / 180)^2): tangent and square in double, rounded once
+float strata_tan2(float deg) {
+    const double t = std::tan((double)deg * 3.14159265358979323846 / 180.0);
+    return (float)(t * t);
+}
+// the rules of cad.h, "stratified evaluation"; names the offending value
+void strata_check_cuts(const char* axis, const float* cuts, int n, double lo, double hi, const char* unit) {
+    require(n >= 0 && n <= CAD_STRATA_MAX_BINS - 1,
+            std::string(axis) + " cuts: " + std::to_string(n) + " given, at most " + std::to_string(CAD_STRATA_MAX_BINS - 1) +
+                " (" + std::to_string(CAD_STRATA_MAX_BINS) + " bins)");
+    for (int j = 0; j < n; ++j) {
+        const float c = cuts[j];
+        require(std::isfinite(c) && (double)c > lo && (double)c < hi,
+                std::string(axis) + " cut " + fmt_float(c) + " is not strictly inside (" + fmt_float(lo) + ", " + fmt_float(hi) +
+                    ") " + unit);
+        require(j == 0 || cuts[j - 1] < c,
+                std::string(axis) + " cuts must be strictly ascending: " + fmt_float(c) + " follows " +
+                    fmt_float(j ? cuts[j - 1] : 0.f));
+    }
+}
+}  // namespace
 
 cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, const cad_eval_config* cfg, int device,
                                 cad_evaluator** out) {
@@ -2101,7 +2140,7 @@ cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, c
         require(c.min_depth > 0.f && c.min_depth < c.max_depth, "evaluator needs 0 < min_depth < max_depth");
         HIPCHK(hipSetDevice(device));
         auto e = std::make_unique<cad_evaluator>();
-        e->device = device; e->Bmax = max_batch; e->capacity = capacity; e->HW = (int64_t)H * W; e->cfg = c;
+        e->device = device; e->Bmax = max_batch; e->capacity = capacity; e->HW = (int64_t)H * W; e->W = W; e->cfg = c;
         e->nb = cad::eval_blocks(e->HW);
         const size_t tb = sizeof(double) * CAD_EVAL_METRICS * (size_t)capacity;
         const size_t pb = sizeof(double) * CAD_EVAL_METRICS * (size_t)max_batch * e->nb;
@@ -2115,6 +2154,7 @@ void cad_evaluator_destroy(cad_evaluator* e) {
     if (!e) return;
     (void)hipFree(e->table);
     if (e->align_mem) (void)hipFree(e->align_mem);
+    if (e->strata_table) (void)hipFree(e->strata_table);
     delete e;
 }
 cad_status cad_evaluator_reset(cad_evaluator* e) {
@@ -2125,11 +2165,30 @@ cad_status cad_evaluator_reset(cad_evaluator* e) {
 }
 cad_status cad_evaluator_update(cad_evaluator* e, const float* pred, const float* gt, const uint8_t* mask, int B,
                                 void* stream) {
+    return cad_evaluator_update_k(e, pred, gt, mask, nullptr, B, stream);
+}
+cad_status cad_evaluator_update_k(cad_evaluator* e, const float* pred, const float* gt, const uint8_t* mask, const float* K,
+                                  int B, void* stream) {
     return guard([&] {
         require(e && pred && gt, "null argument");
         require(B >= 1 && B <= e->Bmax, "batch exceeds the evaluator's max_batch");
         require(e->count + B <= e->capacity, "evaluator capacity exceeded");
+        require(K || e->strata.n_angle_cuts == 0,
+                "the angle strata need the batch's K: use cad_evaluator_update_k (update with K)");
         HIPCHK(hipSetDevice(e->device));
+        if (strata_total_bins(e) > 0) {
+            if (e->align != CAD_ALIGN_NONE)
+                cad::eval_align(e->align, pred, gt, mask, B, e->HW, e->cfg.min_depth, e->cfg.max_depth, e->align_ws, e->nb,
+                                e->align_table, e->align_flags, e->count, S(stream));
+            cad::eval_update_strata(pred, gt, mask, K, B, e->HW, e->W, e->cfg.min_depth, e->cfg.max_depth, e->cfg.clamp_pred,
+                                    e->part, e->nb, e->table, e->count, S(stream),
+                                    e->align != CAD_ALIGN_NONE ? e->align_table : nullptr, e->strata, e->strata_part,
+                                    e->strata_table);
+            HIPCHK(hipGetLastError());
+            e->count += B;
+            e->last = S(stream);
+            return;
+        }
         if (e->align != CAD_ALIGN_NONE)
             cad::eval_align(e->align, pred, gt, mask, B, e->HW, e->cfg.min_depth, e->cfg.max_depth, e->align_ws, e->nb,
                             e->align_table, e->align_flags, e->count, S(stream));
@@ -2214,6 +2273,101 @@ cad_status cad_evaluator_metrics(cad_evaluator* e, float* per_sample, cad_eval_s
         if (st != CAD_OK) return st;
     }
     return cad_eval_finish(sums.data(), e->count, per_sample, s);
+}
+
+// ---------------- stratified evaluation ----------------
+cad_status cad_strata_angle_thresholds(const float* cuts_deg, int n, float* out) {
+    return guard([&] {
+        require(n >= 0 && (n == 0 || (cuts_deg && out)), "bad arguments");
+        strata_check_cuts("angle", cuts_deg, n, 0.0, 90.0, "degrees");
+        for (int j = 0; j < n; ++j) out[j] = strata_tan2(cuts_deg[j]);
+    });
+}
+cad_status cad_evaluator_set_strata(cad_evaluator* e, const cad_strata_config* cfg) {
+    return guard([&] {
+        require(e != nullptr, "null evaluator");
+        require(e->count == 0, "the strata can only change while the evaluator is empty (count == 0)");
+        cad::EvalStrata sp{};
+        if (cfg) {
+            strata_check_cuts("depth", cfg->depth_cuts, cfg->n_depth_cuts, e->cfg.min_depth, e->cfg.max_depth, "metres");
+            strata_check_cuts("angle", cfg->angle_cuts_deg, cfg->n_angle_cuts, 0.0, 90.0, "degrees");
+            sp.n_depth_cuts = cfg->n_depth_cuts;
+            sp.n_angle_cuts = cfg->n_angle_cuts;
+            for (int j = 0; j < sp.n_depth_cuts; ++j) sp.depth_cuts[j] = cfg->depth_cuts[j];
+            for (int j = 0; j < sp.n_angle_cuts; ++j) {
+                sp.angle_cuts[j] = strata_tan2(cfg->angle_cuts_deg[j]);
+                require(j == 0 || sp.angle_cuts[j - 1] < sp.angle_cuts[j],
+                        "angle cut " + fmt_float(cfg->angle_cuts_deg[j]) + " is not distinct from " +
+                            fmt_float(cfg->angle_cuts_deg[j - 1]) + " in fp32 tan^2");
+            }
+        }
+        const int nbt = (sp.n_depth_cuts > 0 ? sp.n_depth_cuts + 1 : 0) + (sp.n_angle_cuts > 0 ? sp.n_angle_cuts + 1 : 0);
+        require(nbt == 0 || e->HW < ((int64_t)1 << 31), "strata need H * W < 2^31");
+        if (nbt > e->strata_alloc_bins) {
+            HIPCHK(hipSetDevice(e->device));
+            const size_t row = sizeof(double) * CAD_EVAL_METRICS * (size_t)nbt;
+            const size_t tb = row * (size_t)e->capacity, pb = row * (size_t)e->Bmax * (size_t)e->nb;
+            void* mem = nullptr;
+            HIPCHK(hipMalloc(&mem, tb + pb));
+            hipError_t err = hipMemset(mem, 0, tb + pb);
+            if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+            if (err != hipSuccess) {
+                (void)hipFree(mem);
+                HIPCHK(err);
+            }
+            if (e->strata_table) (void)hipFree(e->strata_table);
+            e->strata_table = static_cast<double*>(mem);
+            e->strata_alloc_bins = nbt;
+        }
+        if (nbt > 0) e->strata_part = e->strata_table + (size_t)CAD_EVAL_METRICS * nbt * (size_t)e->capacity;
+        e->strata = sp;
+    });
+}
+int cad_evaluator_strata_bins(const cad_evaluator* e, int axis) {
+    return e && (axis == CAD_STRATA_DEPTH || axis == CAD_STRATA_ANGLE) ? strata_axis_bins(e, axis) : 0;
+}
+cad_status cad_evaluator_strata_sums(cad_evaluator* e, int axis, double* out, void* stream) {
+    return guard([&] {
+        require(e && out, "null argument");
+        require(axis == CAD_STRATA_DEPTH || axis == CAD_STRATA_ANGLE, "unknown strata axis " + std::to_string(axis));
+        const int bins = strata_axis_bins(e, axis);
+        require(bins > 0, std::string("the ") + (axis == CAD_STRATA_DEPTH ? "depth" : "angle") + " strata are off");
+        if (e->count == 0) return;
+        HIPCHK(hipSetDevice(e->device));
+        const size_t row = sizeof(double) * CAD_EVAL_METRICS;
+        const size_t pitch = row * (size_t)strata_total_bins(e), width = row * (size_t)bins;
+        const double* src = e->strata_table + (axis == CAD_STRATA_ANGLE ? CAD_EVAL_METRICS * strata_axis_bins(e, CAD_STRATA_DEPTH) : 0);
+        HIPCHK(hipMemcpy2DAsync(out, width, src, pitch, width, (size_t)e->count, hipMemcpyDeviceToHost, S(stream)));
+        HIPCHK(hipStreamSynchronize(S(stream)));
+    });
+}
+cad_status cad_eval_strata_finish(const double* sums, int64_t n, int bins, float* per_sample, cad_eval_summary* per_bin) {
+    return guard([&] {
+        require(n >= 0 && bins >= 1 && bins <= CAD_STRATA_MAX_BINS && (sums || n == 0), "bad arguments");
+        if (per_sample) {
+            double m[CAD_EVAL_METRICS];
+            for (int64_t i = 0; i < n * bins; ++i) {
+                eval_finish_row(sums + i * CAD_EVAL_METRICS, m);
+                for (int k = 0; k < CAD_EVAL_METRICS; ++k) per_sample[i * CAD_EVAL_METRICS + k] = (float)m[k];
+            }
+        }
+        if (!per_bin) return;
+        std::vector<double> present, pooled((size_t)CAD_EVAL_METRICS);
+        for (int b = 0; b < bins; ++b) {
+            present.clear();
+            std::fill(pooled.begin(), pooled.end(), 0.0);
+            for (int64_t i = 0; i < n; ++i) {
+                const double* t = sums + (i * bins + b) * CAD_EVAL_METRICS;
+                for (int k = 0; k < CAD_EVAL_METRICS; ++k) pooled[(size_t)k] += t[k];
+                if (t[0] > 0) present.insert(present.end(), t, t + CAD_EVAL_METRICS);
+            }
+            const cad_status st = cad_eval_finish(present.data(), (int64_t)(present.size() / CAD_EVAL_METRICS), nullptr, &per_bin[b]);
+            if (st != CAD_OK) throw CadError(st, g_err);
+            double pm[CAD_EVAL_METRICS];
+            eval_finish_row(pooled.data(), pm);   // the same sums as the present samples': absent rows are zero
+            for (int k = 0; k < CAD_EVAL_METRICS; ++k) per_bin[b].pooled[k] = (float)pm[k];
+        }
+    });
 }
 
 // ---------------- scale-aligned evaluation ----------------

@@ -712,6 +712,11 @@ const char* cad_dataset_image_dir(const cad_dataset* d, int64_t i) {
     return d->items[(size_t)i].dir.c_str();
 }
 
+const char* cad_dataset_sensor(const cad_dataset* d, int64_t i) {
+    if (!d || i < 0 || i >= d->n) return nullptr;
+    return d->synthetic ? "synthetic" : d->items[(size_t)i].sensor.c_str();
+}
+
 cad_status cad_dataset_read(const cad_dataset* d, int64_t i, uint8_t* rgb, int64_t rgb_cap, uint16_t* depth,
                             int64_t depth_cap, cad_decoded_info* info) {
     return data_guard([&] {

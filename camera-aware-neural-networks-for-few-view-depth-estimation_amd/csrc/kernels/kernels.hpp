@@ -330,6 +330,18 @@ int eval_blocks(int64_t HW);
 void eval_update(const float* pred, const float* gt, const uint8_t* mask, int B, int64_t HW, float min_depth,
                  float max_depth, int clamp_pred, double* part, int nb, double* table, int64_t base, hipStream_t st,
                  const float* align = nullptr);
+// Stratified evaluation (eval_kernels.hip): eval_update plus, in the same pass, the twelve sums per depth
+// bin of gt and per bin of the pixel's ray angle (rho^2 against tan^2 cuts; K: [B][9] device, read when
+// n_angle_cuts > 0).  0 cuts: that axis is off.  nbt = depth bins + angle bins; spart: [B][nb][nbt][12],
+// stable: [rows][nbt][12], depth bins first.  HW < 2^31.
+struct EvalStrata {
+    int n_depth_cuts, n_angle_cuts;
+    float depth_cuts[15];   // metres, ascending
+    float angle_cuts[15];   // tan^2 of the angle cuts, ascending
+};
+void eval_update_strata(const float* pred, const float* gt, const uint8_t* mask, const float* K, int B, int64_t HW, int W,
+                        float min_depth, float max_depth, int clamp_pred, double* part, int nb, double* table, int64_t base,
+                        hipStream_t st, const float* align, const EvalStrata& sp, double* spart, double* stable);
 // Scale alignment of the evaluation (eval_align_kernels.hip; the closed forms are in eval_align.hpp).
 // eval_align writes rows base .. base + B - 1 of `table` ([rows][2] floats {scale, shift}) and of `flags`
 // ([rows] bytes, 0 where a fallback applied) for mode 1 (median: radix select), 2 (log mean) or 3 (least

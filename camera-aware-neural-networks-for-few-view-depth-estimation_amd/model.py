@@ -504,11 +504,18 @@ class Evaluator:
 
     align: "none" | "median" | "log_mean" | "scale_shift" — a per-sample (scale, shift) computed on the
     device from the valid pixels (cad.h, "scale-aligned evaluation"); the metrics then score
-    scale * pred + shift.  alignment() returns the (scale, shift) rows."""
+    scale * pred + shift.  alignment() returns the (scale, shift) rows.
+
+    depth_bins / angle_bins: ascending cuts in metres / in degrees off the optical axis (cad.h, "stratified
+    evaluation"); update() then also keeps the twelve sums per sample and per stratum, strata(axis) returns
+    them.  With angle_bins, update() needs the batch's K."""
 
     def __init__(self, capacity, max_batch, H, W, min_depth=0.1, max_depth=10.0, clamp_pred=True, device=0,
-                 align="none"):
+                 align="none", depth_bins=None, angle_bins=None):
         mode = _abi.eval_align_mode(align)
+        strata = _abi.strata_config(depth_bins, angle_bins)
+        self.min_depth, self.max_depth = float(min_depth), float(max_depth)
+        self._cuts = {"depth": [], "angle": []}
         self.lib = _abi.load()
         self.device = torch.device("cuda", device)
         self.capacity, self.max_batch, self.height, self.width = int(capacity), int(max_batch), int(H), int(W)
@@ -519,6 +526,17 @@ class Evaluator:
         self.h = h
         if mode:
             check(self.lib.cad_evaluator_set_alignment(self.h, mode), "cad_evaluator_set_alignment")
+        if strata.n_depth_cuts or strata.n_angle_cuts:
+            self._set_strata(strata)
+
+    def _set_strata(self, cfg):
+        check(self.lib.cad_evaluator_set_strata(self.h, C.byref(cfg)), "cad_evaluator_set_strata")
+        self._cuts = {"depth": [float(np.float32(c)) for c in cfg.depth_cuts[:cfg.n_depth_cuts]],
+                      "angle": [float(np.float32(c)) for c in cfg.angle_cuts_deg[:cfg.n_angle_cuts]]}
+
+    def set_strata(self, depth_bins=None, angle_bins=None):
+        """Change the strata; allowed only while count == 0 (CadError otherwise, nothing changed)."""
+        self._set_strata(_abi.strata_config(depth_bins, angle_bins))
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -526,8 +544,10 @@ class Evaluator:
             self.lib.cad_evaluator_destroy(h)
             self.h = None
 
-    def update(self, pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | None = None):
-        """Append the B samples of pred / gt (B,1,H,W) [mask: (B,1,H,W), nonzero = valid]."""
+    def update(self, pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | None = None,
+               K: torch.Tensor | None = None):
+        """Append the B samples of pred / gt (B,1,H,W) [mask: (B,1,H,W), nonzero = valid; K: (B,3,3), the
+        batch's intrinsics, required with angle_bins]."""
         B = pred.shape[0]
         assert pred.numel() == gt.numel() == B * self.height * self.width, "pred / gt must be (B,1,H,W)"
         m = None
@@ -535,8 +555,14 @@ class Evaluator:
             assert mask.numel() == pred.numel(), "mask must be (B,1,H,W)"
             mt = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else mask.to(torch.uint8).contiguous()
             m = C.c_void_p(mt.data_ptr())
-        check(self.lib.cad_evaluator_update(self.h, _ptr(pred), _ptr(gt), m, B, _stream(self.device)),
-              "cad_evaluator_update")
+        if K is None:
+            check(self.lib.cad_evaluator_update(self.h, _ptr(pred), _ptr(gt), m, B, _stream(self.device)),
+                  "cad_evaluator_update")
+            return
+        assert K.numel() == B * 9 and K.dtype == torch.float32, "K must be (B,3,3) float32"
+        Kc = K.contiguous()
+        check(self.lib.cad_evaluator_update_k(self.h, _ptr(pred), _ptr(gt), m, _ptr(Kc), B, _stream(self.device)),
+              "cad_evaluator_update_k")
 
     def reset(self):
         check(self.lib.cad_evaluator_reset(self.h), "cad_evaluator_reset")
@@ -575,6 +601,23 @@ class Evaluator:
               "cad_evaluator_sums")
         return out
 
+    def strata_bins(self, axis) -> int:
+        """Bins on "depth" or "angle" (cuts + 1); 0 when the axis is off."""
+        return int(self.lib.cad_evaluator_strata_bins(self.h, _abi.strata_axis(axis)))
+
+    def strata(self, axis) -> dict:
+        """{"edges" (bins + 1 floats: metres, or degrees ending at 90), "sums" (count, bins, 12) float64,
+        "per_sample" (count, bins, 12) float32 metrics, "summary": one dict per bin (count = the samples with
+        a valid pixel in the bin)}.  CadError when the axis is off."""
+        ax = _abi.strata_axis(axis)
+        bins = self.strata_bins(axis)
+        sums = np.zeros((self.count, max(bins, 1), 12), np.float64)
+        check(self.lib.cad_evaluator_strata_sums(self.h, ax, sums.ctypes.data_as(C.POINTER(C.c_double)), _stream(self.device)),
+              "cad_evaluator_strata_sums")
+        per, summary = eval_strata_finish(sums)
+        lo, hi = (self.min_depth, self.max_depth) if axis == "depth" else (0.0, 90.0)
+        return {"edges": [lo] + list(self._cuts[axis]) + [hi], "sums": sums, "per_sample": per, "summary": summary}
+
     def _finish(self):
         per = np.zeros((self.count, 12), np.float32)
         s = _abi.EvalSummary()
@@ -592,6 +635,38 @@ class Evaluator:
         for stat in ("mean", "std", "median", "min", "max", "pooled"):
             out[stat] = {k: float(getattr(s, stat)[i]) for i, k in enumerate(EVAL_KEYS)}
         return out
+
+
+def _summary_dict(s) -> dict:
+    out = {"count": int(s.count)}
+    for stat in ("mean", "std", "median", "min", "max", "pooled"):
+        out[stat] = {k: float(getattr(s, stat)[i]) for i, k in enumerate(EVAL_KEYS)}
+    return out
+
+
+def eval_strata_finish(sums):
+    """cad_eval_strata_finish (host only): (N, bins, 12) sums -> ((N, bins, 12) float32 metrics, [one summary
+    dict per bin]); a bin's statistics run over the samples with a valid pixel in it."""
+    sums = np.ascontiguousarray(sums, np.float64)
+    if sums.ndim != 3 or sums.shape[2] != 12:
+        raise ValueError("sums must be (N, bins, 12)")
+    n, bins = sums.shape[0], sums.shape[1]
+    per = np.zeros((n, bins, 12), np.float32)
+    summ = (_abi.EvalSummary * max(bins, 1))()
+    check(_abi.load().cad_eval_strata_finish(sums.ctypes.data_as(C.POINTER(C.c_double)), n, bins, per.ctypes.data_as(_abi.FP),
+                                             summ), "cad_eval_strata_finish")
+    return per, [_summary_dict(summ[b]) for b in range(bins)]
+
+
+def strata_angle_thresholds(angle_bins) -> np.ndarray:
+    """The fp32 tan^2 thresholds the evaluator compares rho^2 with, for angle cuts in degrees (host only)."""
+    cuts = np.ascontiguousarray(angle_bins, np.float32)
+    if cuts.ndim != 1 or cuts.size > _abi.STRATA_MAX_BINS - 1:
+        raise ValueError(f"angle_bins: {cuts.size} cuts given, at most {_abi.STRATA_MAX_BINS - 1}")
+    out = np.zeros_like(cuts)
+    check(_abi.load().cad_strata_angle_thresholds(cuts.ctypes.data_as(_abi.FP), cuts.size, out.ctypes.data_as(_abi.FP)),
+          "cad_strata_angle_thresholds")
+    return out
 
 
 def depth_metrics_full(pred, gt, mask=None, min_depth=0.1, max_depth=10.0, clamp_pred=True, per_sample=False,
@@ -634,12 +709,14 @@ def _eval_forward(model, rgb, K):
     return model.forward(rgb)
 
 
-def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False, align="none"):
+def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False, align="none",
+             depth_bins=None, angle_bins=None):
     """ModelEvaluator: eval-mode forwards over `batches` of (rgb, gt, K[, mask]) device tensors, every
     prediction scored on device (Evaluator.update) with no host synchronisation inside the loop; the
     model's train / eval mode is restored.  Returns {"keys", "per_sample" (N,12), "summary",
     "forward_ms_per_image" (events around the whole loop), "parameters", "align", "alignment" (N,2)
-    (scale, shift) per sample[, "predictions" (the raw ones)]}."""
+    (scale, shift) per sample[, "predictions" (the raw ones)]}.  depth_bins / angle_bins (Evaluator): also
+    "strata": {"depth" | "angle": Evaluator.strata(axis)} for the axes asked for."""
     _abi.eval_align_mode(align)
     batches = list(batches)
     if not batches:
@@ -648,7 +725,8 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
     dev = batches[0][0].device
     n = sum(int(b[0].shape[0]) for b in batches)
     ev = Evaluator(n, max(int(b[0].shape[0]) for b in batches), H, W, min_depth, max_depth, clamp_pred,
-                   device=dev.index or 0, align=align)
+                   device=dev.index or 0, align=align, depth_bins=depth_bins, angle_bins=angle_bins)
+    with_k = ev.strata_bins("angle") > 0
     was_training = bool(getattr(model, "training", True))
     model.eval()
     preds = []
@@ -658,7 +736,7 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
         for b in batches:
             rgb, gt, K = b[0], b[1], b[2]
             pred = _eval_forward(model, rgb, K)
-            ev.update(pred, gt, b[3] if len(b) > 3 else None)
+            ev.update(pred, gt, b[3] if len(b) > 3 else None, K if with_k else None)
             if keep_predictions:
                 preds.append(pred.clone())
         t1.record()
@@ -670,6 +748,9 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
            "parameters": model.count_parameters(), "align": align, "alignment": ev.alignment()}
     if keep_predictions:
         out["predictions"] = torch.cat(preds)
+    axes = [a for a in ("depth", "angle") if ev.strata_bins(a) > 0]
+    if axes:
+        out["strata"] = {a: ev.strata(a) for a in axes}
     return out
 
 

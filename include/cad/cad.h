@@ -52,6 +52,9 @@
  *                                   src/evaluation/evaluator.h:385-397, on a device-resident table of
  *                                   per-sample sums (the reference's evaluation target does not build;
  *                                   its metric definitions are the contract)
+ *   cad_evaluator_set_strata/update_k/strata_bins/strata_sums, cad_eval_strata_finish
+ *                                   the same sums per depth-range and ray-angle stratum (no reference
+ *                                   counterpart)
  *   cad_evaluator_set_alignment/get_alignment/alignment/aligned, cad_valid_medians,
  *   cad_eval_solve_alignment        per-sample median / log-mean / least-squares alignment of the
  *                                   prediction before the metrics (new: no reference counterpart; the
@@ -489,6 +492,56 @@ cad_status cad_valid_medians(const float* pred, const float* gt, const uint8_t* 
  * The code the device solve kernel runs. */
 cad_status cad_eval_solve_alignment(int mode, const double stats[7], const float med[2], float out2[2]);
 
+/* ---- stratified evaluation.  With strata set, update keeps the same twelve sums per sample and per
+ * stratum on two per-pixel axes, computed on the device in the pass that fills the sample's total row (the
+ * total row keeps its bits; the pixel terms, the valid set and the alignment, which stays per sample over all
+ * its valid pixels, are those of the unstratified evaluator).
+ *   depth axis  cuts c_0 < ... < c_{m-1}, fp32, finite, strictly inside (min_depth, max_depth), 1 <= m <= 15.
+ *               A valid pixel's bin is the number of cuts with c_j <= gt (fp32 comparison): m + 1 bins
+ *               [min, c_0), [c_0, c_1), ..., [c_{m-1}, max).
+ *   angle axis  cuts th_0 < ... < th_{m-1} in degrees, inside (0, 90), 1 <= m <= 15; the host forms
+ *               t_j = (float)(tan(th_j pi / 180)^2), tangent and square in double, rounded once.  With
+ *               u = column, v = row as fp32 values of the integer pixel index and fx = K[0], cx = K[2],
+ *               fy = K[4], cy = K[5] of the sample's row-major K (the K of the H x W batch):
+ *               x = (u - cx) / fx, y = (v - cy) / fy, rho2 = x x + y y, every operation an individually
+ *               rounded fp32 operation, no epsilon.  The bin is the number of cuts with t_j <= rho2 (a NaN
+ *               rho2: bin 0): m + 1 bins, the last one ending at 90 degrees.
+ * On each axis every valid pixel lies in exactly one bin: per sample n and the three delta counts add over
+ * the bins to the total row exactly, the eight real sums within double rounding.  A sample's stratum rows
+ * are the same bits on every run, in whichever batch it arrives, from aligned or unaligned tensors (no
+ * floating-point atomics; fixed reduction order). */
+#define CAD_STRATA_MAX_BINS 16
+#define CAD_STRATA_DEPTH 0
+#define CAD_STRATA_ANGLE 1
+typedef struct {
+    int n_depth_cuts;                              /* 0: the depth axis is off */
+    float depth_cuts[CAD_STRATA_MAX_BINS - 1];     /* metres */
+    int n_angle_cuts;                              /* 0: the angle axis is off */
+    float angle_cuts_deg[CAD_STRATA_MAX_BINS - 1]; /* degrees off the optical axis */
+} cad_strata_config;
+/* allowed only while count == 0; every rule above is checked before any device call and the message names
+ * the offending value.  Allocates the strata table (capacity x bins x 12 doubles per axis) and the partials
+ * here, so that update still allocates nothing.  cfg NULL or both axes with 0 cuts: strata off.  On an
+ * error nothing changes. */
+cad_status cad_evaluator_set_strata(cad_evaluator* e, const cad_strata_config* cfg);
+/* cad_evaluator_update with the batch's K (B,3,3) device fp32: the required form while the angle axis is on
+ * (cad_evaluator_update is then CAD_ERR_INVALID, table and count unchanged).  K may be NULL while the angle
+ * axis is off.  With strata set three kernels on `stream` instead of two; no allocation, no synchronisation. */
+cad_status cad_evaluator_update_k(cad_evaluator* e, const float* pred, const float* gt, const uint8_t* mask,
+                                  const float* K, int B, void* stream);
+/* bins on an axis (cuts + 1), 0 when the axis is off */
+int cad_evaluator_strata_bins(const cad_evaluator* e, int axis);
+/* host copy of the axis's first count rows: count x bins x 12 doubles; one synchronous copy on `stream` */
+cad_status cad_evaluator_strata_sums(cad_evaluator* e, int axis, double* out, void* stream);
+/* host only: the tan^2 thresholds t_j of n angle cuts in degrees, as the evaluator forms them */
+cad_status cad_strata_angle_thresholds(const float* cuts_deg, int n, float* out);
+/* host only: n x bins rows of twelve sums -> per-sample, per-bin metrics (n x bins x 12, nullable) and one
+ * summary per bin (bins, nullable), the formulas of cad_eval_finish with one difference: a bin's mean / std /
+ * median / min / max run over the samples with at least one valid pixel in that bin, and count is their
+ * number (an image without a pixel in the stratum says nothing about it); pooled adds all samples' sums.
+ * A bin no sample reaches: count 0 and zeros. */
+cad_status cad_eval_strata_finish(const double* sums, int64_t n, int bins, float* per_sample, cad_eval_summary* per_bin);
+
 /* ---- conditioning: per-pixel unit ray directions (B,3,H,W) from K (B,3,3) ---- */
 cad_status cad_ray_directions(const float* K, int B, int H, int W, float* rays, void* stream);
 
@@ -564,6 +617,8 @@ cad_status cad_dataset_synthetic(int64_t n, int height, int width, uint32_t seed
 void cad_dataset_destroy(cad_dataset* d);
 int64_t cad_dataset_size(const cad_dataset* d);
 const char* cad_dataset_image_dir(const cad_dataset* d, int64_t i); /* NULL for synthetic */
+/* the sample's manifest sensor_type ("synthetic" for the synthetic dataset); NULL out of range */
+const char* cad_dataset_sensor(const cad_dataset* d, int64_t i);
 /* host decode of sample i into rgb (h0*w0*3 bytes) and depth (dh0*dw0 u16); either may be NULL to
  * query info only */
 cad_status cad_dataset_read(const cad_dataset* d, int64_t i, uint8_t* rgb, int64_t rgb_cap, uint16_t* depth,

@@ -60,6 +60,30 @@ inline bool parseAlignment(const std::string& s, Alignment* out) {
     return false;
 }
 
+// Stratified evaluation (cad.h, "stratified evaluation"): the per-pixel axes and one axis's result
+enum class StrataAxis { Depth = CAD_STRATA_DEPTH, Angle = CAD_STRATA_ANGLE };
+struct StrataResult {
+    int bins = 0;                            // 0: the axis was off
+    std::vector<float> edges;                // bins + 1: metres, or degrees ending at 90
+    std::vector<double> sums;                // count x bins x 12
+    std::vector<float> per_sample;           // count x bins x 12 metrics, metricKeys() order
+    std::vector<cad_eval_summary> summary;   // per bin, over the samples with a valid pixel in it
+};
+// cad_strata_config of two cut lists (empty: that axis is off); more than 15 cuts throw, naming the count
+inline cad_strata_config strataConfig(const std::vector<float>& depth_cuts, const std::vector<float>& angle_cuts_deg) {
+    cad_strata_config c{};
+    const auto fill = [](const char* what, const std::vector<float>& v, int* n, float* out) {
+        if (v.size() > (size_t)CAD_STRATA_MAX_BINS - 1)
+            throw std::runtime_error(std::string(what) + " cuts: " + std::to_string(v.size()) + " given, at most " +
+                                     std::to_string(CAD_STRATA_MAX_BINS - 1));
+        *n = (int)v.size();
+        for (size_t j = 0; j < v.size(); ++j) out[j] = v[j];
+    };
+    fill("depth", depth_cuts, &c.n_depth_cuts, c.depth_cuts);
+    fill("angle", angle_cuts_deg, &c.n_angle_cuts, c.angle_cuts_deg);
+    return c;
+}
+
 // RAII handle of a cad_evaluator
 class MetricsTable {
 public:
@@ -79,6 +103,42 @@ public:
     // asynchronous on `stream`: no allocation, no host synchronisation
     void update(const DeviceTensor& pred, const DeviceTensor& gt, const uint8_t* mask = nullptr, void* stream = nullptr) {
         cad::check(cad_evaluator_update(h_, pred.data, gt.data, mask, (int)pred.size(0), stream), "cad_evaluator_update");
+    }
+    // the form with the batch's K (B,3,3): required while the angle strata are on
+    void update(const DeviceTensor& pred, const DeviceTensor& gt, const uint8_t* mask, const DeviceTensor& K, void* stream = nullptr) {
+        cad::check(cad_evaluator_update_k(h_, pred.data, gt.data, mask, K.data, (int)pred.size(0), stream), "cad_evaluator_update_k");
+    }
+    // allowed only while count() == 0; allocates the strata table, so that update still allocates nothing
+    void setStrata(const std::vector<float>& depth_cuts, const std::vector<float>& angle_cuts_deg) {
+        const cad_strata_config c = strataConfig(depth_cuts, angle_cuts_deg);
+        cad::check(cad_evaluator_set_strata(h_, &c), "cad_evaluator_set_strata");
+        depth_cuts_ = depth_cuts;
+        angle_cuts_ = angle_cuts_deg;
+    }
+    int strataBins(StrataAxis axis) const { return cad_evaluator_strata_bins(h_, (int)axis); }
+    // one axis's sums, metrics and per-bin summaries; one synchronous copy on `stream` (bins == 0: axis off)
+    StrataResult strata(StrataAxis axis, float lo, float hi, void* stream = nullptr) {
+        StrataResult r;
+        r.bins = strataBins(axis);
+        if (r.bins == 0) return r;
+        const std::vector<float>& cuts = axis == StrataAxis::Depth ? depth_cuts_ : angle_cuts_;
+        r.edges.push_back(lo);
+        r.edges.insert(r.edges.end(), cuts.begin(), cuts.end());
+        r.edges.push_back(hi);
+        const size_t n = (size_t)count() * (size_t)r.bins * CAD_EVAL_METRICS;
+        r.sums.assign(n, 0.0);
+        r.per_sample.assign(n, 0.f);
+        r.summary.resize((size_t)r.bins);
+        cad::check(cad_evaluator_strata_sums(h_, (int)axis, r.sums.data(), stream), "cad_evaluator_strata_sums");
+        cad::check(cad_eval_strata_finish(r.sums.data(), count(), r.bins, r.per_sample.data(), r.summary.data()),
+                   "cad_eval_strata_finish");
+        return r;
+    }
+    // the table's twelve sums per sample (count x 12); one synchronous copy on `stream`
+    std::vector<double> sums(void* stream = nullptr) {
+        std::vector<double> s((size_t)count() * CAD_EVAL_METRICS);
+        cad::check(cad_evaluator_sums(h_, s.data(), stream), "cad_evaluator_sums");
+        return s;
     }
     void reset() { cad::check(cad_evaluator_reset(h_), "cad_evaluator_reset"); }
     int64_t count() const { return cad_evaluator_count(h_); }
@@ -106,6 +166,7 @@ public:
 
 private:
     cad_evaluator* h_ = nullptr;
+    std::vector<float> depth_cuts_, angle_cuts_;
 };
 
 struct DepthMetricsFull {
@@ -243,6 +304,10 @@ struct EvaluationConfig {
     int batch_size = 8;
     int device = 0;
     int64_t max_samples = -1;   // -1: the whole loader
+    // stratified evaluation (cad.h): cuts in metres / in degrees off the optical axis (empty: axis off), and
+    // whether the result carries each sample's sensor
+    std::vector<float> depth_cuts, angle_cuts_deg;
+    bool by_sensor = false;
     // called after each batch's update with (index of its first sample, predictions (n,1,H,W), n).  A
     // callback that copies to the host synchronises; without one the loop never does.
     std::function<void(int64_t, const DeviceTensor&, int)> on_batch;
@@ -257,6 +322,9 @@ struct EvaluationResult {
     MetricMap mean_metrics, std_metrics, median_metrics, min_metrics, max_metrics, pooled_metrics;
     double forward_ms_per_image = 0.0;   // HIP events around the whole loop / samples
     int64_t num_parameters = 0;
+    StrataResult depth_strata, angle_strata;   // bins == 0 unless EvaluationConfig asked for the axis
+    std::vector<double> sums;                  // count x 12, filled with by_sensor or strata
+    std::vector<std::string> sensors;          // one per sample, filled with by_sensor
 };
 
 class ModelEvaluator {
@@ -310,6 +378,8 @@ public:
         cam_ = DeviceTensor::empty({B, 4}, d);
         rays_ = DeviceTensor();
         MetricsTable table(ns, B, H, W, config_.min_depth, config_.max_depth, config_.clamp_pred, d, config_.align);
+        const bool strata = !config_.depth_cuts.empty() || !config_.angle_cuts_deg.empty();
+        if (strata) table.setStrata(config_.depth_cuts, config_.angle_cuts_deg);
         cad_loader* ring = L.ring(B, d, false);
         cad::check(cad_loader_start_epoch(ring, nullptr, ns), "evaluation");
         cad_event *t0 = nullptr, *t1 = nullptr;
@@ -326,7 +396,8 @@ public:
                 if (n == 0) break;   // the loader's end of epoch: the loop's only host-visible event
                 for (DeviceTensor* t : {&rgb_, &gt_, &K_, &pred_, &cam_}) t->shape[0] = n;
                 forward_(n);
-                table.update(pred_, gt_);
+                if (strata) table.update(pred_, gt_, nullptr, K_);
+                else table.update(pred_, gt_);
                 if (config_.on_batch) config_.on_batch(first, pred_, n);
                 first += n;
             }
@@ -335,6 +406,13 @@ public:
             r.per_sample = table.metrics(&s);
             r.align = config_.align;
             r.alignment = table.alignment(&r.aligned);
+            if (strata) {
+                r.depth_strata = table.strata(StrataAxis::Depth, config_.min_depth, config_.max_depth);
+                r.angle_strata = table.strata(StrataAxis::Angle, 0.f, 90.f);
+            }
+            if (strata || config_.by_sensor) r.sums = table.sums();
+            if (config_.by_sensor)
+                for (int64_t i = 0; i < table.count(); ++i) r.sensors.push_back(L.sensor(i));
             float ms = 0.f;
             cad::check(cad_event_elapsed_ms(t0, t1, &ms), "event");
             r.forward_ms_per_image = (double)ms / (double)std::max<int64_t>(1, table.count());

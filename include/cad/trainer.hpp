@@ -83,6 +83,12 @@ public:
         return L;
     }
     size_t size() const { return (size_t)cad_dataset_size(ds_.get()); }
+    // sample i's manifest sensor_type ("synthetic" for the synthetic dataset)
+    std::string sensor(int64_t i) const {
+        const char* s = cad_dataset_sensor(ds_.get(), i);
+        if (!s) throw std::runtime_error("SunRGBDLoader::sensor: no sample " + std::to_string(i));
+        return s;
+    }
     void enableAugmentation(const AugmentationConfig& c) { aug_ = c; augment_ = true; rings_.clear(); }
     void disableAugmentation() { augment_ = false; rings_.clear(); }
     bool augmentation_enabled() const { return augment_; }
