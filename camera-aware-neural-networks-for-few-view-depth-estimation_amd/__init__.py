@@ -22,7 +22,7 @@ def __getattr__(name):
     if name == "lr_at":
         from . import recipe
         return recipe.lr_at
-    if name in ("BatchAssembler", "AugSampler", "SunRGBDDataset", "PrefetchLoader"):
+    if name in ("BatchAssembler", "AugSampler", "SunRGBDDataset", "PrefetchLoader", "color_matrix"):
         from . import batch
         return getattr(batch, name)
     if name in ("Predictor", "save_png", "load_png", "encode_png", "decode_png", "save_ply", "colormap_lut", "POINT_DTYPE"):

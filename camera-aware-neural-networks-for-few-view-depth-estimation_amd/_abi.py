@@ -303,6 +303,7 @@ SIGNATURES = {
     "cad_aug_sampler_create": (I, [C.c_void_p, C.c_uint32, C.POINTER(P)]),
     "cad_aug_sampler_destroy": (None, [P]),
     "cad_aug_sampler_draw": (I, [P, I, I, C.c_void_p]),
+    "cad_color_matrix": (I, [F, F, FP]),
     "cad_loss_forward_backward_masked": (I, [P, P, P, P, P, P, I, P, P, P]),
     "cad_comm_get_unique_id": (I, [C.c_void_p]),
     "cad_comm_create": (I, [C.c_void_p, I, I, I, C.POINTER(P)]),
@@ -383,7 +384,8 @@ class Sample(C.Structure):
     """cad_sample (cad.h): one decoded sample and its augmentation parameters."""
     _fields_ = [("rgb", P), ("depth", P), ("h0", I), ("w0", I), ("bgr", I), ("depth_scale", F),
                 ("K", F * 9), ("aug", I), ("crop", I), ("crop_scale", F), ("crop_x", I), ("crop_y", I),
-                ("flip", I), ("jitter", I), ("brightness", F), ("contrast", F), ("dh0", I), ("dw0", I)]
+                ("flip", I), ("jitter", I), ("brightness", F), ("contrast", F), ("dh0", I), ("dw0", I),
+                ("color", I), ("saturation", F), ("hue", F), ("gamma_on", I), ("gamma", F)]
 
 
 class DecodedInfo(C.Structure):
@@ -392,10 +394,12 @@ class DecodedInfo(C.Structure):
 
 
 class AugConfig(C.Structure):
-    """cad_aug_config = AugmentationConfig (sunrgbd_loader.h:30-42), defaults as there."""
+    """cad_aug_config = AugmentationConfig (sunrgbd_loader.h:30-42), defaults as there; the declared stages
+    (saturation_delta, hue_delta, enable_random_gamma, gamma_min, gamma_max) default to 0 / off."""
     _fields_ = [("enable_random_crop", I), ("crop_scale_min", F), ("crop_scale_max", F),
                 ("enable_horizontal_flip", I), ("horizontal_flip_prob", F), ("enable_color_jitter", I),
-                ("brightness_delta", F), ("contrast_delta", F)]
+                ("brightness_delta", F), ("contrast_delta", F), ("saturation_delta", F), ("hue_delta", F),
+                ("enable_random_gamma", I), ("gamma_min", F), ("gamma_max", F)]
 
     def __init__(self, **kw):
         d = dict(enable_random_crop=1, crop_scale_min=0.7, crop_scale_max=1.0, enable_horizontal_flip=1,

@@ -24,9 +24,20 @@ def _stream(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def color_matrix(saturation: float, hue: float):
+    """The fp32 3x3 matrix the batcher applies for a sample's (saturation, hue) (cad_color_matrix): a scaling
+    by `saturation` and a rotation by 2 pi `hue` of the YIQ chroma plane.  (1, 0) is the identity."""
+    import numpy as np
+    m = (C.c_float * 9)()
+    check(_abi.load().cad_color_matrix(saturation, hue, m), "cad_color_matrix")
+    return np.array(list(m), np.float32).reshape(3, 3)
+
+
 class AugSampler:
     """augmentSample's random draws (std::mt19937 seeded with config.random_seed, same distributions in
-    the same order: crop scale, crop x, crop y, flip, brightness, contrast)."""
+    the same order: crop scale, crop x, crop y, flip, brightness, contrast), then the declared stages'
+    (saturation_delta, hue_delta, enable_random_gamma + gamma_min / gamma_max; off by default): saturation,
+    hue, gamma."""
 
     def __init__(self, seed: int = 42, **config):
         self.lib = _abi.load()
@@ -39,7 +50,8 @@ class AugSampler:
         s = _abi.Sample()
         check(self.lib.cad_aug_sampler_draw(self.h, height, width, C.byref(s)), "cad_aug_sampler_draw")
         return {k: getattr(s, k) for k in ("aug", "crop", "crop_scale", "crop_x", "crop_y", "flip", "jitter",
-                                           "brightness", "contrast")}
+                                           "brightness", "contrast", "color", "saturation", "hue", "gamma_on",
+                                           "gamma")}
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -52,7 +64,8 @@ class BatchAssembler:
 
     A sample is a dict: rgb (uint8 HWC device tensor), depth (16-bit HW device tensor), K (3x3),
     optional bgr (default 0), depth_scale (default 1/1000) and augmentation fields (AugSampler.draw,
-    or aug=0 / absent for resize only)."""
+    or aug=0 / absent for resize only; color / saturation / hue and gamma_on / gamma, absent = off, are the
+    declared colour stages of cad.h's cad_sample)."""
 
     def __init__(self, max_batch: int, height: int, width: int, device: int = 0):
         self.lib = _abi.load()
@@ -80,10 +93,11 @@ class BatchAssembler:
             K = torch.as_tensor(s["K"], dtype=torch.float32).reshape(9)
             for e in range(9):
                 a.K[e] = float(K[e])
-            for k in ("aug", "crop", "crop_x", "crop_y", "flip", "jitter"):
+            for k in ("aug", "crop", "crop_x", "crop_y", "flip", "jitter", "color", "gamma_on"):
                 setattr(a, k, int(s.get(k, 0)))
-            for k in ("crop_scale", "brightness", "contrast"):
+            for k in ("crop_scale", "brightness", "contrast", "saturation", "gamma"):
                 setattr(a, k, float(s.get(k, 1.0)))
+            a.hue = float(s.get("hue", 0.0))
         dev = torch.device("cuda", self.device)
         if out is None:
             out = (torch.empty((B, 3, self.H, self.W), device=dev), torch.empty((B, 1, self.H, self.W), device=dev),

@@ -22,7 +22,10 @@
 // optimization.recipe: declared (or --recipe declared) honours the recipe the config declares — optimizer
 // adam / adamw / sgd, lr_scheduler none / step / cosine with warmup, early_stopping, checkpointing.keep_last_n /
 // save_best_only, validation.primary_metric and an EMA of the weights (ema: {enabled, decay}) — where the
-// default, reference, trains Adam at a constant rate as the reference's running trainer does.
+// default, reference, trains Adam at a constant rate as the reference's running trainer does;
+// data.augmentation.mode: declared (or --augmentation declared) likewise honours the augmentation keys the
+// reference parses and never applies — saturation, hue, random_gamma / gamma_range (cad.h, cad_sample) — and
+// --preview-augmentation DIR writes what the train loader produces for the first samples instead of training.
 #include <signal.h>
 #include <spawn.h>
 #include <sys/wait.h>
@@ -59,6 +62,9 @@ struct Args {
     bool debug = false, tensorboard = true;
     bool dry_run = false;   // print the (per-rank) run plan and exit before any GPU call
     std::string recipe;     // --recipe reference|declared ("" = the config's optimization.recipe)
+    std::string augmentation;   // --augmentation reference|declared ("" = the config's data.augmentation.mode)
+    std::string preview_dir;    // --preview-augmentation DIR: write the first preview_count train samples, no training
+    int preview_count = 8;
     std::vector<std::string> argv;
 };
 
@@ -77,6 +83,11 @@ void usage() {
                  "      --recipe arg      reference: Adam at a constant rate, whatever the config declares (default);\n"
                  "                        declared: honour optimization.optimizer / lr_scheduler / warmup, early_stopping,\n"
                  "                        checkpointing.keep_last_n / save_best_only and ema (overrides optimization.recipe)\n"
+                 "      --augmentation arg reference: crop, flip, brightness / contrast as the reference applies them (default);\n"
+                 "                        declared: also data.augmentation saturation, hue, random_gamma / gamma_range\n"
+                 "                        (overrides data.augmentation.mode)\n"
+                 "      --preview-augmentation DIR  Write DIR/sample_<i>.png (resized original | augmented) and DIR/draws.csv\n"
+                 "                        for the first --preview-count N (default 8) train samples and exit; no training\n"
                  "  -h, --help            Print help\n";
 }
 
@@ -103,6 +114,16 @@ Args parse_args(int argc, char** argv) {
             a.recipe = next();
             if (a.recipe != "reference" && a.recipe != "declared")
                 throw std::runtime_error("--recipe '" + a.recipe + "': expected reference or declared");
+        }
+        else if (k == "--augmentation") {
+            a.augmentation = next();
+            if (a.augmentation != "reference" && a.augmentation != "declared")
+                throw std::runtime_error("--augmentation '" + a.augmentation + "': expected reference or declared");
+        }
+        else if (k == "--preview-augmentation") a.preview_dir = next();
+        else if (k == "--preview-count") {
+            a.preview_count = std::stoi(next());
+            if (a.preview_count < 1) throw std::runtime_error("--preview-count: must be at least 1");
         }
         else if (k == "--tensorboard") {
             std::string t = (!v.empty() || (i + 1 < argc && argv[i + 1][0] != '-')) ? next() : "true";
@@ -132,6 +153,11 @@ struct Config {   // the TrainingConfig fields the step uses (trainer.h:24-92)
     // data.augmentation (train_main.cpp:377-386 -> AugmentationConfig, random_seed 42)
     bool aug_crop = true, aug_flip = true, aug_jitter = true;
     float aug_flip_p = 0.5f, aug_brightness = 0.2f, aug_contrast = 0.2f;
+    // data.augmentation.mode: declared — the keys augmentSample ignores (load_declared_augmentation)
+    std::string aug_mode = "reference";
+    float aug_saturation = 0.2f, aug_hue = 0.1f;
+    bool aug_gamma = false;
+    float aug_gamma_lo = 0.8f, aug_gamma_hi = 1.2f;
     // hardware: (configs/train_config.yaml:176-183; parsed but unused by the reference)
     bool distributed = false;
     int num_gpus = 1;
@@ -292,6 +318,7 @@ Config load_config(const yaml_lite::Node& y, const std::string& experiment) {   
             c.aug_jitter = a["color_jitter"].as<bool>(true);
             c.aug_brightness = a["brightness"].as<float>(0.2f);
             c.aug_contrast = a["contrast"].as<float>(0.2f);
+            c.aug_mode = a["mode"].as<std::string>("reference");
         }
     }
     if (auto& hw = y["hardware"]) {
@@ -304,6 +331,65 @@ Config load_config(const yaml_lite::Node& y, const std::string& experiment) {   
     c.log_dir += "/" + c.experiment_name;
     load_recipe(y, c);
     return c;
+}
+
+// data.augmentation saturation / hue / random_gamma / gamma_range, read and judged only in declared mode (with
+// the reference mode these keys are ignored, whatever they hold): "Error: data.augmentation.<key> ..." before
+// any GPU call
+void load_declared_augmentation(const yaml_lite::Node& y, Config& c) {
+    if (c.aug_mode == "reference") return;
+    if (c.aug_mode != "declared")
+        throw std::runtime_error("data.augmentation.mode '" + c.aug_mode + "': expected reference or declared");
+    if (!y["data"] || !y["data"]["augmentation"]) return;
+    auto& a = y["data"]["augmentation"];
+    c.aug_saturation = a["saturation"].as<float>(0.2f);
+    c.aug_hue = a["hue"].as<float>(0.1f);
+    c.aug_gamma = a["random_gamma"].as<bool>(false);
+    const std::vector<float> g = a["gamma_range"].as<std::vector<float>>({0.8f, 1.2f});
+    if (!(c.aug_saturation >= 0.f && c.aug_saturation <= 1.f))
+        throw std::runtime_error("data.augmentation.saturation '" + float_text(c.aug_saturation) + "': must be in [0, 1]");
+    if (!(c.aug_hue >= 0.f && c.aug_hue <= 0.5f))
+        throw std::runtime_error("data.augmentation.hue '" + float_text(c.aug_hue) + "': must be in [0, 0.5]");
+    if (g.size() != 2) throw std::runtime_error("data.augmentation.gamma_range: expected two values [lo, hi]");
+    c.aug_gamma_lo = g[0];
+    c.aug_gamma_hi = g[1];
+    if (c.aug_gamma && !(std::isfinite(g[0]) && std::isfinite(g[1]) && g[0] > 0.f && g[0] <= g[1]))
+        throw std::runtime_error("data.augmentation.gamma_range [" + float_text(g[0]) + ", " + float_text(g[1]) +
+                                 "]: expected 0 < lo <= hi");
+}
+
+AugmentationConfig augmentation_of(const Config& c) {
+    AugmentationConfig ac;
+    ac.enable_random_crop = c.aug_crop;
+    ac.enable_horizontal_flip = c.aug_flip;
+    ac.horizontal_flip_prob = c.aug_flip_p;
+    ac.enable_color_jitter = c.aug_jitter;
+    ac.brightness_delta = c.aug_brightness;
+    ac.contrast_delta = c.aug_contrast;
+    if (c.aug_mode == "declared") {
+        ac.declared = true;
+        ac.saturation_delta = c.aug_saturation;
+        ac.hue_delta = c.aug_hue;
+        ac.enable_random_gamma = c.aug_gamma;
+        ac.gamma_min = c.aug_gamma_lo;
+        ac.gamma_max = c.aug_gamma_hi;
+    }
+    return ac;
+}
+
+// the ranges a declared run draws from, one line (--dry-run, and the start of a run)
+std::string declared_augmentation_text(const Config& c) {
+    std::ostringstream o;
+    o << "Augmentation (declared): ";
+    if (c.dataset == "synthetic") return o.str() + "the synthetic dataset is not augmented";
+    if (c.aug_jitter)
+        o << "saturation [" << float_text(1.0f - c.aug_saturation) << ", " << float_text(1.0f + c.aug_saturation) << "], hue ["
+          << float_text(-c.aug_hue) << ", " << float_text(c.aug_hue) << "]";
+    else
+        o << "saturation and hue off (color_jitter: false)";
+    if (c.aug_gamma) o << ", gamma [" << float_text(c.aug_gamma_lo) << ", " << float_text(c.aug_gamma_hi) << "]";
+    else o << ", gamma off";
+    return o.str();
 }
 
 bool ends_with(const std::string& s, const std::string& suf) {
@@ -486,6 +572,71 @@ int dry_run(const Config& c, const Rank& r, bool tensorboard) {
     }
     o << "}";
     std::cout << o.str() << std::endl;
+    if (c.aug_mode == "declared" && r.rank == 0) std::cout << declared_augmentation_text(c) << std::endl;
+    return 0;
+}
+
+// --preview-augmentation: the first n samples of the train loader in manifest order, each through its batch-1
+// rings — without augmentation (the resized original) and with it, the draws being the ones a run's first n
+// samples get — as 8-bit strips `original | augmented`, and the draws themselves as draws.csv.
+int preview_augmentation(const Args& args, const Config& c, SunRGBDLoader& L, int device) {
+    const int H = c.height, W = c.width;
+    const int64_t n = std::min<int64_t>(args.preview_count, (int64_t)L.size());
+    const size_t HW = (size_t)H * W;
+    fs::create_directories(args.preview_dir);
+    void *rgb = nullptr, *depth = nullptr, *K = nullptr;
+    cad::check(cad_malloc(device, (int64_t)(3 * HW * sizeof(float)), &rgb), "preview buffer");
+    cad::check(cad_malloc(device, (int64_t)(HW * sizeof(float)), &depth), "preview buffer");
+    cad::check(cad_malloc(device, 9 * sizeof(float), &K), "preview buffer");
+    std::shared_ptr<void> free_rgb(rgb, cad_free), free_depth(depth, cad_free), free_K(K, cad_free);
+    std::vector<float> plain(3 * HW * (size_t)n), aug(3 * HW);
+    auto fetch = [&](cad_loader* ring, float* host) {
+        const int b = cad_loader_next(ring, (float*)rgb, (float*)depth, (float*)K, nullptr);
+        if (b != 1) throw std::runtime_error(std::string("data loader: ") + (b < 0 ? cad_last_error() : "epoch ended early"));
+        cad::check(cad_memcpy(host, rgb, (int64_t)(3 * HW * sizeof(float)), 1, nullptr), "preview d2h");
+    };
+    cad_loader* ring = L.ring(1, device, false);
+    cad::check(cad_loader_start_epoch(ring, nullptr, n), "preview");
+    for (int64_t i = 0; i < n; ++i) fetch(ring, plain.data() + 3 * HW * (size_t)i);
+    // the sampler of the augmented ring, restated: same config, same seed, drawn in sample order
+    cad_aug_sampler* sampler = nullptr;
+    const cad_aug_config ac = L.aug_config();
+    if (L.augmentation_enabled())
+        cad::check(cad_aug_sampler_create(&ac, (uint32_t)L.augmentation().random_seed, &sampler), "preview sampler");
+    std::shared_ptr<cad_aug_sampler> free_sampler(sampler, cad_aug_sampler_destroy);
+    std::ofstream csv(args.preview_dir + "/draws.csv");
+    csv << "index,crop_scale,crop_x,crop_y,flip,brightness,contrast,saturation,hue,gamma\n";
+    ring = L.ring(1, device, true);
+    cad::check(cad_loader_start_epoch(ring, nullptr, n), "preview");
+    std::vector<uint8_t> strip(HW * 6), png;
+    auto level = [](float v) { return (uint8_t)std::lround(std::min(1.f, std::max(0.f, v)) * 255.f); };
+    for (int64_t i = 0; i < n; ++i) {
+        fetch(ring, aug.data());
+        cad_sample d{};
+        if (sampler) cad::check(cad_aug_sampler_draw(sampler, H, W, &d), "preview draw");
+        csv << i << "," << float_text(d.crop ? d.crop_scale : 1.f) << "," << (d.crop ? d.crop_x : 0) << "," << (d.crop ? d.crop_y : 0)
+            << "," << d.flip << "," << float_text(d.jitter ? d.brightness : 1.f) << "," << float_text(d.jitter ? d.contrast : 1.f)
+            << "," << float_text(d.color ? d.saturation : 1.f) << "," << float_text(d.color ? d.hue : 0.f) << ","
+            << float_text(d.gamma_on ? d.gamma : 1.f) << "\n";
+        const float* o = plain.data() + 3 * HW * (size_t)i;
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x)
+                for (int ch = 0; ch < 3; ++ch) {
+                    const size_t src = (size_t)ch * HW + (size_t)y * W + x, dst = ((size_t)y * 2 * W + x) * 3 + ch;
+                    strip[dst] = level(o[src]);
+                    strip[dst + 3 * (size_t)W] = level(aug[src]);
+                }
+        int64_t cap = 0, size = 0;
+        cad::check(cad_png_encode(strip.data(), H, 2 * W, 3, 8, nullptr, 0, &cap), "cad_png_encode");
+        png.resize((size_t)cap);
+        cad::check(cad_png_encode(strip.data(), H, 2 * W, 3, 8, png.data(), cap, &size), "cad_png_encode");
+        const std::string path = args.preview_dir + "/sample_" + std::to_string(i) + ".png";
+        std::ofstream f(path, std::ios::binary);
+        f.write(reinterpret_cast<const char*>(png.data()), (std::streamsize)size);
+        if (!f) throw std::runtime_error("cannot write " + path);
+    }
+    if (!csv) throw std::runtime_error("cannot write " + args.preview_dir + "/draws.csv");
+    std::cout << "Augmentation preview (" << c.aug_mode << "): " << n << " samples in " << args.preview_dir << "\n";
     return 0;
 }
 
@@ -504,9 +655,12 @@ int run(const Args& args) {
     c.recipe.learning_rate = c.learning_rate;
     c.recipe.weight_decay = c.weight_decay;
     check_recipe(c);
+    if (!args.augmentation.empty()) c.aug_mode = args.augmentation;   // the flag overrides data.augmentation.mode
+    load_declared_augmentation(y, c);
     if (c.distributed && c.backend != "nccl" && c.backend != "rccl")
         throw std::runtime_error("hardware.backend '" + c.backend + "': this build exchanges gradients over RCCL (\"nccl\")");
-    if (c.distributed && c.num_gpus > 1 && !std::getenv(kEnvRank)) return launch_ranks(args, c);
+    const bool preview = !args.preview_dir.empty();   // one process, whatever hardware.* says
+    if (c.distributed && c.num_gpus > 1 && !std::getenv(kEnvRank) && !preview) return launch_ranks(args, c);
     const Rank R = rank_of_process(c, args);
     // the dataset: "synthetic" = generated batches; anything else = the SUN RGB-D manifest through the
     // prefetch ring (cad_dataset / cad_loader: decode on host threads, pinned double-buffered upload,
@@ -532,6 +686,7 @@ int run(const Args& args) {
         std::cout << "Recipe (declared): optimizer " << c.recipe.optimizer << ", lr_scheduler " << c.recipe.lr_scheduler
                   << " (warmup " << c.recipe.lr_warmup_epochs << " epochs), ema decay " << c.recipe.ema_decay
                   << ", early stopping " << (c.recipe.use_early_stopping ? "on" : "off") << "\n";
+    if (lead && c.aug_mode == "declared") std::cout << declared_augmentation_text(c) << "\n";
     if (args.debug && lead) std::cout << "Debug mode enabled - using reduced dataset\n";
     int ndev = 0;
     cad::check(cad_device_count(&ndev), "device query");
@@ -548,20 +703,14 @@ int run(const Args& args) {
             train_loader->filterBySensorType(c.sensor_types);
             val_loader->filterBySensorType(c.sensor_types);
         }
-        AugmentationConfig ac;
-        ac.enable_random_crop = c.aug_crop;
-        ac.enable_horizontal_flip = c.aug_flip;
-        ac.horizontal_flip_prob = c.aug_flip_p;
-        ac.enable_color_jitter = c.aug_jitter;
-        ac.brightness_delta = c.aug_brightness;
-        ac.contrast_delta = c.aug_contrast;
-        train_loader->enableAugmentation(ac);
+        train_loader->enableAugmentation(augmentation_of(c));
     } else {   // disjoint generated splits
         train_loader = SunRGBDLoader::synthetic(c.n_train, c.height, c.width, (uint32_t)c.seed);
         if (c.n_val > 0) val_loader = SunRGBDLoader::synthetic(c.n_val, c.height, c.width, (uint32_t)c.seed + 1);
     }
     for (auto& L : {train_loader, val_loader})
         if (L) L->setTargetDimensions(c.height, c.width);
+    if (preview) return preview_augmentation(args, c, *train_loader, R.device);
 
     cad::Workspace ws{c.batch_size, c.height, c.width, R.device};
     if (c.architecture == "geometry_aware") {   // single-process GeometryTrainer (trainer.hpp)

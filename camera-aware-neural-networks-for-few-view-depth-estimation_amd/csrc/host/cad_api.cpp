@@ -2500,6 +2500,36 @@ void cad_batcher_destroy(cad_batcher* b) {
     delete b;
 }
 
+// The saturation / hue matrix (cad.h): M = T^-1 D T in double, as I + T^-1 (D - I) T — D - I vanishes at
+// (1, 0), so that pair gives the identity exactly — rounded to fp32.  T^-1 is the adjugate inverse in double.
+static void color_matrix(float saturation, float hue, float out[9]) {
+    static const double T[3][3] = {{0.299, 0.587, 0.114}, {0.595716, -0.274453, -0.321263}, {0.211456, -0.522591, 0.311135}};
+    double Ti[3][3];
+    const double det = T[0][0] * (T[1][1] * T[2][2] - T[1][2] * T[2][1]) - T[0][1] * (T[1][0] * T[2][2] - T[1][2] * T[2][0]) +
+                       T[0][2] * (T[1][0] * T[2][1] - T[1][1] * T[2][0]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {   // cofactor of T[j][i]
+            const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+            Ti[i][j] = (T[r0][c0] * T[r1][c1] - T[r0][c1] * T[r1][c0]) / det;
+        }
+    const double th = 2.0 * 3.14159265358979323846 * (double)hue, s = (double)saturation;
+    const double cs = s * std::cos(th), sn = s * std::sin(th);
+    const double E[3][3] = {{0, 0, 0}, {0, cs - 1.0, -sn}, {0, sn, cs - 1.0}};   // D - I
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0;
+            for (int k = 1; k < 3; ++k) acc += Ti[i][k] * (E[k][1] * T[1][j] + E[k][2] * T[2][j]);
+            out[3 * i + j] = (float)((i == j ? 1.0 : 0.0) + acc);
+        }
+}
+cad_status cad_color_matrix(float saturation, float hue, float out[9]) {
+    return guard([&] {
+        require(out, "null argument");
+        require(std::isfinite(saturation) && std::isfinite(hue), "saturation and hue must be finite");
+        color_matrix(saturation, hue, out);
+    });
+}
+
 cad_status cad_batcher_assemble(cad_batcher* b, const cad_sample* samples, int B, float* rgb, float* depth, float* K,
                                 void* stream) {
     return guard([&] {
@@ -2509,7 +2539,7 @@ cad_status cad_batcher_assemble(cad_batcher* b, const cad_sample* samples, int B
         HIPCHK(hipEventSynchronize(b->staged));   // the staging buffer is free again
         const int H = b->H, W = b->W;
         float* Kh = reinterpret_cast<float*>(b->host + b->Bmax);
-        bool any_aug = false;
+        bool any_aug = false, any_color = false;
         for (int i = 0; i < B; ++i) {
             const cad_sample& s = samples[i];
             require(s.rgb && s.depth && s.h0 >= 1 && s.w0 >= 1, "sample " + std::to_string(i) + ": no image");
@@ -2548,6 +2578,17 @@ cad_status cad_batcher_assemble(cad_batcher* b, const cad_sample* samples, int B
             if (s.jitter) {   // applyColorJitter :432-443
                 d.jitter = 1; d.contrast = s.contrast; d.brightness = s.brightness;
             }
+            if (s.color) {   // the declared saturation / hue: one matrix per sample
+                require(std::isfinite(s.saturation) && std::isfinite(s.hue),
+                        "sample " + std::to_string(i) + ": saturation and hue must be finite");
+                d.color = 1;
+                color_matrix(s.saturation, s.hue, d.m);
+            }
+            if (s.gamma_on) {
+                require(std::isfinite(s.gamma) && s.gamma > 0.f, "sample " + std::to_string(i) + ": gamma must be positive and finite");
+                d.gamma_on = 1; d.gamma = s.gamma;
+            }
+            any_color = any_color || d.color || d.gamma_on;
             if (d.ch != H || d.cw != W) {   // the second resizeSample (getSample :165)
                 const float sx = static_cast<float>(W) / d.cw, sy = static_cast<float>(H) / d.ch;
                 k[0] = k[0] * sx; k[4] = k[4] * sy; k[2] = k[2] * sx; k[5] = k[5] * sy;
@@ -2558,7 +2599,7 @@ cad_status cad_batcher_assemble(cad_batcher* b, const cad_sample* samples, int B
         HIPCHK(hipEventRecord(b->staged, S(stream)));
         float* rgb_tmp = b->tmp;
         float* depth_tmp = b->tmp + 3 * (size_t)b->Bmax * H * W;
-        cad::batch_assemble(b->dev, B, H, W, any_aug, rgb, depth, rgb_tmp, depth_tmp, S(stream));
+        cad::batch_assemble(b->dev, B, H, W, any_aug, any_color, rgb, depth, rgb_tmp, depth_tmp, S(stream));
         HIPCHK(hipGetLastError());
     });
 }
@@ -2573,6 +2614,12 @@ cad_status cad_aug_sampler_create(const cad_aug_config* cfg, uint32_t seed, cad_
         require(cfg && out, "null argument");
         require(cfg->crop_scale_min > 0.f && cfg->crop_scale_min <= cfg->crop_scale_max && cfg->crop_scale_max <= 1.f,
                 "crop scale range must satisfy 0 < min <= max <= 1");
+        require(cfg->saturation_delta >= 0.f && cfg->saturation_delta <= 1.f, "saturation_delta must be in [0, 1]");
+        require(cfg->hue_delta >= 0.f && cfg->hue_delta <= 0.5f, "hue_delta must be in [0, 0.5]");
+        if (cfg->enable_random_gamma) {
+            require(std::isfinite(cfg->gamma_min) && cfg->gamma_min > 0.f, "gamma_min must be positive and finite");
+            require(std::isfinite(cfg->gamma_max) && cfg->gamma_max >= cfg->gamma_min, "gamma_max must be finite and at least gamma_min");
+        }
         auto s = std::make_unique<cad_aug_sampler>();
         s->cfg = *cfg;
         s->rng.seed(seed);
@@ -2607,6 +2654,24 @@ cad_status cad_aug_sampler_draw(cad_aug_sampler* s, int height, int width, cad_s
             std::uniform_real_distribution<float> cd(1.0f - c.contrast_delta, 1.0f + c.contrast_delta);
             smp->brightness = bd(s->rng);
             smp->contrast = cd(s->rng);
+        }
+        // the declared stages, after augmentSample's own draws (all off: the engine advances as the reference's)
+        smp->color = 0; smp->saturation = 1.f; smp->hue = 0.f;
+        if (c.enable_color_jitter && c.saturation_delta > 0.f) {
+            std::uniform_real_distribution<float> sd(1.0f - c.saturation_delta, 1.0f + c.saturation_delta);
+            smp->saturation = sd(s->rng);
+            smp->color = 1;
+        }
+        if (c.enable_color_jitter && c.hue_delta > 0.f) {
+            std::uniform_real_distribution<float> hd(-c.hue_delta, c.hue_delta);
+            smp->hue = hd(s->rng);
+            smp->color = 1;
+        }
+        smp->gamma_on = c.enable_random_gamma ? 1 : 0;
+        smp->gamma = 1.f;
+        if (c.enable_random_gamma) {
+            std::uniform_real_distribution<float> gd(c.gamma_min, c.gamma_max);
+            smp->gamma = gd(s->rng);
         }
     });
 }

@@ -17,6 +17,9 @@
 //
 // Work: ~30 B of HBM traffic per output pixel (u8 gather + fp32 writes, plus one fp32 round trip for
 // augmented samples): far below the step's cost, so one thread per output pixel and no tiling.
+// The declared colour stages (cad.h, cad_sample: saturation / hue matrix, gamma — not in the reference's
+// augmentSample) add no traffic, only arithmetic per source tap: 9 products and, with gamma, 3 powf
+// (DESIGN.md §3.3 has the measured time).
 #include <algorithm>
 
 #include "kernels.hpp"
@@ -87,8 +90,33 @@ __global__ void k_batch_resize(const BatchSample* __restrict__ smp, int H, int W
     }
 }
 
+// The declared colour stages of one source tap (cad.h, cad_sample): the three channels together, after the
+// jitter.  Saturation / hue: one 3x3 matrix per sample (a rotation and scaling of the YIQ chroma plane, built
+// on the host), three products and two sums kept apart so that an fp32 restatement is bit-exact; then gamma on
+// the clamped value.
+struct Rgb {
+    float r, g, b;
+};
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+__device__ __forceinline__ float mat_row(const float* m, const Rgb& v) {
+    // (__fmul_rn / __fadd_rn are inline functions over the plain operators, which the compiler contracts at will;
+    // the pragma binds the operators written in its scope, so they are spelled out here)
+#pragma clang fp contract(off)
+    const float p0 = m[0] * v.r, p1 = m[1] * v.g, p2 = m[2] * v.b;
+    return clamp01((p0 + p1) + p2);
+}
+__device__ __forceinline__ Rgb color_tap(const float* __restrict__ src, int64_t HW, int64_t idx, const BatchSample& s) {
+    Rgb v{jitter(src[idx], s), jitter(src[HW + idx], s), jitter(src[2 * HW + idx], s)};
+    if (s.color) v = Rgb{mat_row(s.m, v), mat_row(s.m + 3, v), mat_row(s.m + 6, v)};
+    if (s.gamma_on) v = Rgb{powf(clamp01(v.r), s.gamma), powf(clamp01(v.g), s.gamma), powf(clamp01(v.b), s.gamma)};
+    return v;
+}
+
 // stage 2 (augmented samples): crop [cy, cy+ch) x [cx, cx+cw) of the stage-1 image, optional
-// horizontal flip, colour jitter, resize back to H x W
+// horizontal flip, colour jitter, resize back to H x W.  kColor: the instantiation that also knows the
+// declared colour stages, launched only when some sample of the batch has one; its samples without them
+// take the same arithmetic as the other instantiation.
+template <bool kColor>
 __global__ void k_batch_augment(const BatchSample* __restrict__ smp, int H, int W, const float* __restrict__ rgb_tmp,
                                 const float* __restrict__ depth_tmp, float* __restrict__ rgb_out,
                                 float* __restrict__ depth_out) {
@@ -96,6 +124,8 @@ __global__ void k_batch_augment(const BatchSample* __restrict__ smp, int H, int 
     const BatchSample& s = smp[b];
     if (!s.aug) return;
     const int64_t HW = (int64_t)H * W;
+    const bool staged = kColor && (s.color || s.gamma_on);   // uniform over the block
+    const bool one_tap = s.ch == H && s.cw == W;              // no second resize: the four taps coincide
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += (int64_t)gridDim.x * blockDim.x) {
         const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
         const Lin ly = lin_axis(y, s.ch, H), lx = lin_axis(x, s.cw, W);
@@ -103,12 +133,27 @@ __global__ void k_batch_augment(const BatchSample* __restrict__ smp, int H, int 
         auto col = [&](int j) { return s.cx + (s.flip ? s.cw - 1 - j : j); };
         const int64_t y0 = s.cy + ly.i0, y1 = s.cy + ly.i1;
         const int c0 = col(lx.i0), c1 = col(lx.i1);
+        if (staged) {
+            const float* src = rgb_tmp + (int64_t)b * 3 * HW;
+            float* out = rgb_out + (int64_t)b * 3 * HW + p;
+            const Rgb v00 = color_tap(src, HW, y0 * W + c0, s);
+            if (one_tap) {   // lerp2(v, v, v, v) with weights (1, 0) is v
+                out[0] = v00.r; out[HW] = v00.g; out[2 * HW] = v00.b;
+            } else {
+                const Rgb v01 = color_tap(src, HW, y0 * W + c1, s), v10 = color_tap(src, HW, y1 * W + c0, s),
+                          v11 = color_tap(src, HW, y1 * W + c1, s);
+                out[0] = lerp2(v00.r, v01.r, v10.r, v11.r, ly, lx);
+                out[HW] = lerp2(v00.g, v01.g, v10.g, v11.g, ly, lx);
+                out[2 * HW] = lerp2(v00.b, v01.b, v10.b, v11.b, ly, lx);
+            }
+        } else {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float* src = rgb_tmp + ((int64_t)b * 3 + c) * HW;
-            const float x00 = jitter(src[y0 * W + c0], s), x01 = jitter(src[y0 * W + c1], s);
-            const float x10 = jitter(src[y1 * W + c0], s), x11 = jitter(src[y1 * W + c1], s);
-            rgb_out[((int64_t)b * 3 + c) * HW + p] = lerp2(x00, x01, x10, x11, ly, lx);
+            for (int c = 0; c < 3; ++c) {
+                const float* src = rgb_tmp + ((int64_t)b * 3 + c) * HW;
+                const float x00 = jitter(src[y0 * W + c0], s), x01 = jitter(src[y0 * W + c1], s);
+                const float x10 = jitter(src[y1 * W + c0], s), x11 = jitter(src[y1 * W + c1], s);
+                rgb_out[((int64_t)b * 3 + c) * HW + p] = lerp2(x00, x01, x10, x11, ly, lx);
+            }
         }
         const int ny = nearest_axis(y, s.ch, H), nx = nearest_axis(x, s.cw, W);
         depth_out[(int64_t)b * HW + p] = depth_tmp[(int64_t)b * HW + (int64_t)(s.cy + ny) * W + col(nx)];
@@ -117,13 +162,15 @@ __global__ void k_batch_augment(const BatchSample* __restrict__ smp, int H, int 
 
 }  // namespace
 
-void batch_assemble(const BatchSample* samples_dev, int B, int H, int W, bool any_aug, float* rgb, float* depth,
-                    float* rgb_tmp, float* depth_tmp, hipStream_t st) {
+void batch_assemble(const BatchSample* samples_dev, int B, int H, int W, bool any_aug, bool any_color, float* rgb,
+                    float* depth, float* rgb_tmp, float* depth_tmp, hipStream_t st) {
     const int64_t HW = (int64_t)H * W;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (HW + 255) / 256)), (unsigned)B);
     hipLaunchKernelGGL(k_batch_resize, grid, dim3(256), 0, st, samples_dev, H, W, rgb, depth, rgb_tmp, depth_tmp);
-    if (any_aug)
-        hipLaunchKernelGGL(k_batch_augment, grid, dim3(256), 0, st, samples_dev, H, W, rgb_tmp, depth_tmp, rgb, depth);
+    if (any_aug && any_color)
+        hipLaunchKernelGGL(k_batch_augment<true>, grid, dim3(256), 0, st, samples_dev, H, W, rgb_tmp, depth_tmp, rgb, depth);
+    else if (any_aug)
+        hipLaunchKernelGGL(k_batch_augment<false>, grid, dim3(256), 0, st, samples_dev, H, W, rgb_tmp, depth_tmp, rgb, depth);
 }
 
 }  // namespace cad

@@ -428,9 +428,14 @@ struct BatchSample {
     int cy, cx, ch, cw;      // crop window of the H x W stage-1 image (already clamped to it)
     int flip, jitter;
     float contrast, brightness;
+    int color;               // declared stages: saturation / hue matrix m (row-major), after the jitter
+    float m[9];
+    int gamma_on;            // then powf(v, gamma)
+    float gamma;
 };
-void batch_assemble(const BatchSample* samples_dev, int B, int H, int W, bool any_aug, float* rgb, float* depth,
-                    float* rgb_tmp, float* depth_tmp, hipStream_t st);
+// any_color: some augmented sample has color / gamma_on (else the stage-2 kernel without those stages runs)
+void batch_assemble(const BatchSample* samples_dev, int B, int H, int W, bool any_aug, bool any_color, float* rgb,
+                    float* depth, float* rgb_tmp, float* depth_tmp, hipStream_t st);
 
 // ---------------- conditioning (cond_kernels.hip, film_kernels.hip) ----------------
 void ray_directions(const float* K, int B, int H, int W, float* rays_nchw, hipStream_t st);

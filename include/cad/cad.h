@@ -66,6 +66,9 @@
  *                                   batch torch::stack + .to(device) (enhanced.h:277-289), on device
  *   cad_aug_sampler_create/draw     augmentSample's random draws (sunrgbd_loader.cpp:352-443;
  *                                   AugmentationConfig sunrgbd_loader.h:30-42, rng_ seed :185)
+ *   cad_color_matrix                the declared saturation / hue / gamma stages (new: the reference parses
+ *                                   data.augmentation saturation, hue, random_gamma and applies none of
+ *                                   them; off unless a cad_sample / cad_aug_config asks: "batch assembly")
  *   cad_exporter_* / cad_colormap_lut / cad_png_encode / cad_png_decode / cad_ply_write / cad_hflip /
  *   cad_flip_mean                   DepthVisualizer (src/visualization/depth_viz.h:23-148,
  *                                   depth_visualizer.h) on the device, 16-bit depth PNGs, point clouds
@@ -549,7 +552,13 @@ cad_status cad_ray_directions(const float* K, int B, int H, int W, float* rays, 
  * (B,3,3) K.  Per sample: rgb = u8/255, depth = u16 * depth_scale, resized to H x W (rgb bilinear,
  * align_corners = false; depth nearest; K scaled), then — when aug is set — crop (window clamped to
  * the image like a torch Slice, K's principal point shifted), horizontal flip (cx = W - cx - 1),
- * colour jitter clamp(rgb * contrast + brightness - 1, 0, 1), and the resize back to H x W. */
+ * colour jitter clamp(rgb * contrast + brightness - 1, 0, 1), and the resize back to H x W.
+ *
+ * The declared colour stages (data.augmentation saturation / hue / random_gamma, which the reference parses
+ * and never applies; all-zero fields = the behaviour above).  They act on rgb only, per source tap of the
+ * resize back, after the jitter: with `color`, c' = clamp((M[c][0] r + M[c][1] g) + M[c][2] b, 0, 1) in
+ * unfused fp32 with M = cad_color_matrix(saturation, hue); with `gamma_on`, v' = powf(v, gamma), gamma > 0,
+ * finite.  Depth and K are those of the same sample without them. */
 typedef struct {
     const uint8_t* rgb;     /* device: decoded image, HWC u8, h0 x w0 x 3 */
     const uint16_t* depth;  /* device: decoded depth, HW u16 */
@@ -565,6 +574,10 @@ typedef struct {
     int jitter;             /* applyColorJitter with brightness, contrast */
     float brightness, contrast;
     int dh0, dw0;           /* depth map size when it differs from the image's (0: h0 x w0) */
+    int color;              /* saturation / hue matrix cad_color_matrix(saturation, hue) (needs aug) */
+    float saturation, hue;  /* blend factor around 1; fraction of the colour circle */
+    int gamma_on;           /* powf(v, gamma) (needs aug) */
+    float gamma;
 } cad_sample;
 typedef struct cad_batcher cad_batcher;
 cad_status cad_batcher_create(int max_batch, int height, int width, int device, cad_batcher** out);
@@ -580,14 +593,25 @@ typedef struct { /* AugmentationConfig (sunrgbd_loader.h:30-42) */
     float horizontal_flip_prob; /* 0.5 */
     int enable_color_jitter;
     float brightness_delta, contrast_delta; /* 0.2, 0.2 */
+    /* the declared stages (0 / off: augmentSample's draws, bit for bit) */
+    float saturation_delta, hue_delta; /* in [0, 1] and [0, 0.5]; drawn when enable_color_jitter */
+    int enable_random_gamma;
+    float gamma_min, gamma_max; /* 0 < min <= max */
 } cad_aug_config;
 typedef struct cad_aug_sampler cad_aug_sampler;
-/* std::mt19937 seeded like the loader's rng_ (config.random_seed) */
+/* std::mt19937 seeded like the loader's rng_ (config.random_seed); a bad range fails with a message
+ * naming the field */
 cad_status cad_aug_sampler_create(const cad_aug_config* cfg, uint32_t seed, cad_aug_sampler** out);
 void cad_aug_sampler_destroy(cad_aug_sampler* s);
 /* fills sample->aug/crop/flip/jitter fields with augmentSample's draws, in its order, for an image
- * already resized to height x width */
+ * already resized to height x width; then, from the same engine through uniform_real_distribution<float>:
+ * saturation ~ U[1 - ds, 1 + ds] (enable_color_jitter and ds > 0), hue ~ U[-dh, dh] (enable_color_jitter
+ * and dh > 0), gamma ~ U[gamma_min, gamma_max] (enable_random_gamma) */
 cad_status cad_aug_sampler_draw(cad_aug_sampler* s, int height, int width, cad_sample* sample);
+/* host only: the fp32 matrix the batcher applies for (saturation, hue), row-major.  M = T^-1 D T, T the NTSC
+ * RGB -> YIQ matrix, D = diag(1, s R(2 pi hue)), evaluated in double as I + T^-1 (D - I) T (so that (1, 0) is
+ * exactly the identity) and rounded; rows sum to 1 (grey stays grey) */
+cad_status cad_color_matrix(float saturation, float hue, float out[9]);
 
 /* ---- the loader: SunRGBDLoader's manifest + decoding (src/data/sunrgbd_loader.cpp:39-102, 221-275)
  * and a prefetch ring into the batcher.  cad_dataset_open reads the JSON manifest: "images" entries

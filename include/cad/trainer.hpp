@@ -49,7 +49,9 @@
 
 namespace camera_aware_depth {
 
-struct AugmentationConfig {   // sunrgbd_loader.h:31-46 (saturation / hue are parsed, unused by augmentSample)
+// sunrgbd_loader.h:31-46.  augmentSample ignores saturation / hue (and the configs' random_gamma): they reach the
+// batcher only when `declared` is set (build/train: data.augmentation.mode: declared; cad.h, cad_sample).
+struct AugmentationConfig {
     bool enable_random_crop = true;
     float crop_scale_min = 0.7f;
     float crop_scale_max = 1.0f;
@@ -61,6 +63,10 @@ struct AugmentationConfig {   // sunrgbd_loader.h:31-46 (saturation / hue are pa
     float saturation_delta = 0.2f;
     float hue_delta = 0.1f;
     int random_seed = 42;
+    bool enable_random_gamma = false;
+    float gamma_min = 0.8f;
+    float gamma_max = 1.2f;
+    bool declared = false;   // honour saturation_delta / hue_delta / random gamma
 };
 
 // SUN RGB-D samples from the JSON manifest (valid entries of the allowed sensor types with an
@@ -102,14 +108,9 @@ public:
     }
     const std::string& manifest_path() const { return manifest_; }
     cad_dataset* handle() const { return ds_.get(); }
-
-    // The batch pipeline behind getBatch: a prefetch ring of `batch`-sample batches on `device`
-    // (augmented when augmentation is enabled and `augment`), created on first use.
-    cad_loader* ring(int batch, int device, bool augment) {
-        const bool aug = augment && augment_;
-        const auto key = std::make_tuple(batch, device, aug);
-        for (auto& r : rings_)
-            if (r.first == key) return r.second.get();
+    // what the augmented rings' sampler is created from (seed: augmentation().random_seed)
+    const AugmentationConfig& augmentation() const { return aug_; }
+    cad_aug_config aug_config() const {
         cad_aug_config ac{};
         ac.enable_random_crop = aug_.enable_random_crop;
         ac.crop_scale_min = aug_.crop_scale_min;
@@ -119,6 +120,24 @@ public:
         ac.enable_color_jitter = aug_.enable_color_jitter;
         ac.brightness_delta = aug_.brightness_delta;
         ac.contrast_delta = aug_.contrast_delta;
+        if (aug_.declared) {
+            ac.saturation_delta = aug_.saturation_delta;
+            ac.hue_delta = aug_.hue_delta;
+            ac.enable_random_gamma = aug_.enable_random_gamma;
+            ac.gamma_min = aug_.gamma_min;
+            ac.gamma_max = aug_.gamma_max;
+        }
+        return ac;
+    }
+
+    // The batch pipeline behind getBatch: a prefetch ring of `batch`-sample batches on `device`
+    // (augmented when augmentation is enabled and `augment`), created on first use.
+    cad_loader* ring(int batch, int device, bool augment) {
+        const bool aug = augment && augment_;
+        const auto key = std::make_tuple(batch, device, aug);
+        for (auto& r : rings_)
+            if (r.first == key) return r.second.get();
+        const cad_aug_config ac = aug_config();
         const int threads = (int)std::max(2u, std::min(8u, std::thread::hardware_concurrency()));
         cad_loader* L = nullptr;
         cad::check(cad_loader_create(ds_.get(), batch, h_, w_, aug ? &ac : nullptr, (uint32_t)aug_.random_seed, threads,
