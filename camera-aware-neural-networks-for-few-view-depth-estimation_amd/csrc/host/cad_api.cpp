@@ -122,6 +122,10 @@ struct Conv {
     int pidx = -1, cin = 0, cout = 0;
     float* wd = nullptr;   // dgrad repack
     void *ws = nullptr, *wds = nullptr;   // pre-split weights / dgrad repack (cin % 8 == 0 only)
+    // S3 window kernels' weight twins (cad::conv3x3_wtwin_*): forward / dgrad repack, and their tile widths
+    // (0: the window kernels do not serve that direction of this conv)
+    void *wt = nullptr, *wtd = nullptr;
+    int wt_bn = 0, wtd_bn = 0;
 };
 struct Film {
     int p0 = -1;   // index of film.fc1.weight; the 12 FiLM parameters follow in registration order
@@ -415,6 +419,13 @@ void layout(cad_unet* h, Arena& a) {
         c.ws = sp(n);
         if (dgrad) c.wds = sp(n);
     };
+    // weight twins of the S3 window kernels, whatever the engine at create (it can change afterwards)
+    auto conv_wtwin_alloc = [&](Conv& c, int l, bool dgrad) {
+        c.wt_bn = cad::conv3x3_wtwin_bn(c.cin, h->Wl(l), c.cout);
+        if (c.wt_bn) c.wt = a.take((size_t)cad::conv3x3_wtwin_bytes(c.cin, c.cout));
+        c.wtd_bn = dgrad ? cad::conv3x3_wtwin_bn(c.cout, h->Wl(l), c.cin) : 0;
+        if (c.wtd_bn) c.wtd = a.take((size_t)cad::conv3x3_wtwin_bytes(c.cout, c.cin));
+    };
     h->flat_p = a.f(h->n_flat);
     h->flat_g = a.f(h->n_flat);
     h->norm_coef = a.f(4);
@@ -431,6 +442,8 @@ void layout(cad_unet* h, Arena& a) {
         e.c2.wd = a.f((int64_t)e.c2.cout * 9 * e.c2.cin);
         conv_split_alloc(e.c1, l > 0);
         conv_split_alloc(e.c2, true);
+        conv_wtwin_alloc(e.c1, l, l > 0);
+        conv_wtwin_alloc(e.c2, l, true);
         if (l < 4) { h->cat[l] = a.f(2 * MC); h->cats[l] = sp(2 * MC); }
         if (l > 0) {
             h->pool[l] = a.f(h->Ml(l, B) * h->Cl(l - 1));
@@ -454,6 +467,8 @@ void layout(cad_unet* h, Arena& a) {
         d.c2.wd = a.f((int64_t)d.c2.cout * 9 * d.c2.cin);
         conv_split_alloc(d.c1, true);
         conv_split_alloc(d.c2, true);
+        conv_wtwin_alloc(d.c1, l, true);
+        conv_wtwin_alloc(d.c2, l, true);
         h->up[l].wf = a.f((int64_t)4 * h->up[l].cout * h->up[l].cin);
         h->up[l].wfs = sp((int64_t)4 * h->up[l].cout * h->up[l].cin);
         h->up[l].wms = sp((int64_t)4 * h->up[l].cout * h->up[l].cin);
@@ -599,6 +614,10 @@ void wprep_add(cad::WPrepList& L, int kind, const float* src, float* d32, void* 
     cad::WPrepJob& j = L.job[L.njobs++];
     j.src = src; j.d32 = d32; j.d16 = d16; j.kind = kind; j.cout = cout; j.cin = cin; j.n = n;
 }
+void wprep_twin_add(cad::WPrepList& L, int kind, const float* src, void* twin, int cout, int cin, int bn) {
+    wprep_add(L, kind, src, nullptr, twin, cout, cin, (int64_t)cout * 9 * cin);
+    L.job[L.njobs - 1].bn = bn;
+}
 // forward weights, every forward (they change per step), in one launch: the ConvT forward repack
 // [q][co][ci] (rows 4*cout, K = cin) and, with pre-split operands, the bf16 twins of the conv weights
 // and of that repack
@@ -614,9 +633,18 @@ void prep_fwd_weights(const cad_unet* h, bool ps, hipStream_t st) {
         };
         for (int l = 0; l < 5; ++l) { sw(h->enc[l].c1); sw(h->enc[l].c2); }
         for (int l = 0; l < 4; ++l) { sw(h->dec[l].c1); sw(h->dec[l].c2); }
+    } else if (cad::conv3x3_wtwin_on()) {
+        auto tw = [&](const Conv& c) {
+            if (c.wt) wprep_twin_add(L, cad::WPREP_WTWIN_FWD, h->P(c.pidx), c.wt, c.cout, c.cin, c.wt_bn);
+        };
+        for (int l = 0; l < 5; ++l) { tw(h->enc[l].c1); tw(h->enc[l].c2); }
+        for (int l = 0; l < 4; ++l) { tw(h->dec[l].c1); tw(h->dec[l].c2); }
     }
     cad::weight_prep(L, st);
 }
+// the conv's weight twin when the S3 window kernels read it this call (fwd_wtwin / dgrad_wtwin)
+const void* fwd_wtwin(const Conv& c) { return cad::conv3x3_wtwin_on() ? c.wt : nullptr; }
+const void* dgrad_wtwin(const Conv& c) { return cad::conv3x3_wtwin_on() ? c.wtd : nullptr; }
 
 // in_s / out_s: split twins of the block input / output (p == nullptr: none)
 // out_f32 = false: with pre-split GEMMs downstream only the output's twin is read (decoder outputs
@@ -674,7 +702,8 @@ void double_conv_fwd(cad_unet* h, DoubleConv& dc, const float* in, int64_t ldin,
     if (ps1) {
         cad::conv3x3_fwd_ps(in_s, dc.c1.cin, sv(dc.c1.ws, 9 * dc.c1.cin), C, dc.y1, C, 0, B, Hh, Ww, stats, st, dc.y1b);
     } else {
-        cad::conv3x3_fwd(in, ldin, 0, dc.c1.cin, h->P(dc.c1.pidx), C, dc.y1, C, 0, B, Hh, Ww, stats, st);
+        cad::conv3x3_fwd(in, ldin, 0, dc.c1.cin, h->P(dc.c1.pidx), C, dc.y1, C, 0, B, Hh, Ww, stats, st,
+                         ps ? nullptr : fwd_wtwin(dc.c1));
     }
     bn(dc.b1, dc.c1.cin, ps1);
     if (dc.has_film()) {   // FiLMDoubleConvImpl::forward (intrinsics_unet.h:38-52)
@@ -689,7 +718,7 @@ void double_conv_fwd(cad_unet* h, DoubleConv& dc, const float* in, int64_t ldin,
     if (ps)
         cad::conv3x3_fwd_ps(sv(dc.a1s, C), C, sv(dc.c2.ws, 9 * C), C, dc.y2, C, 0, B, Hh, Ww, stats, st, true);
     else
-        cad::conv3x3_fwd(dc.a1, C, 0, C, h->P(dc.c2.pidx), C, dc.y2, C, 0, B, Hh, Ww, stats, st);
+        cad::conv3x3_fwd(dc.a1, C, 0, C, h->P(dc.c2.pidx), C, dc.y2, C, 0, B, Hh, Ww, stats, st, fwd_wtwin(dc.c2));
     bn(dc.b2, C, ps);
     if (head_pred && att_head) {
         cad::cbam_head_fwd(cbam_view(h, 0), cbam_head_view(h), B, Hh, Ww, head_pred, h->dscr, st);
@@ -896,8 +925,9 @@ void double_conv_bwd(cad_unet* h, DoubleConv& dc, const float* g, int64_t ldg, i
     } else {
         cad::conv3x3_wgrad(dY, C, dc.a1, C, 0, C, h->G(dc.c2.pidx), B, Hh, Ww, h->slab, h->slab_cap, wg);
         HIPCHK(hipEventRecord(h->evA, wg));
-        if (bs.part) bn1_tiles = cad::conv3x3_dgrad_bnsums(dY, C, dc.c2.wd, C, dA1, C, B, Hh, Ww, bs, st);
-        if (!bn1_tiles) cad::conv3x3_dgrad(dY, C, dc.c2.wd, C, dA1, C, B, Hh, Ww, st);
+        const void* tw = dgrad_wtwin(dc.c2);
+        if (bs.part) bn1_tiles = cad::conv3x3_dgrad_bnsums(dY, C, dc.c2.wd, C, dA1, C, B, Hh, Ww, bs, st, tw);
+        if (!bn1_tiles) cad::conv3x3_dgrad(dY, C, dc.c2.wd, C, dA1, C, B, Hh, Ww, st, tw);
     }
     // FiLM: dgamma/dbeta per (sample, channel); the ReLU sees dA1 * gamma (folded into bn_relu_bwd).  By
     // default the FiLM sums come from bn1's backward reduction pass over the same (dA1, y1) (round 4;
@@ -941,15 +971,17 @@ void double_conv_bwd(cad_unet* h, DoubleConv& dc, const float* g, int64_t ldg, i
                                                     Ww, st, din_bf16, din_hi, dc.c1.cin / 2, dc.c1.cin / 2);
             if (din_hi_done) *din_hi_done = done && din_hi;
         } else
-            cad::conv3x3_dgrad(dY1, C, dc.c1.wd, dc.c1.cin, din, lddin, B, Hh, Ww, st);
+            cad::conv3x3_dgrad(dY1, C, dc.c1.wd, dc.c1.cin, din, lddin, B, Hh, Ww, st, ps ? nullptr : dgrad_wtwin(dc.c1));
     }
 }
 
 void repack_dgrad_weights(cad_unet* h, hipStream_t st) {   // one launch (prep_fwd_weights)
     const bool ps = h->fwd_np > 0 && h->fwd_np == cad::split_planes();
     cad::WPrepList L{};
+    const bool twins = !ps && cad::conv3x3_wtwin_on();
     auto rp = [&](Conv& c) {   // dgrad repack [ci][tap][co]: rows cin, K = 9*cout
         wprep_add(L, cad::WPREP_DGRAD, h->P(c.pidx), c.wd, ps ? c.wds : nullptr, c.cout, c.cin, (int64_t)c.cout * 9 * c.cin);
+        if (twins && c.wtd) wprep_twin_add(L, cad::WPREP_WTWIN_DGRAD, h->P(c.pidx), c.wtd, c.cout, c.cin, c.wtd_bn);
     };
     for (int l = 0; l < 5; ++l) {
         if (l > 0) rp(h->enc[l].c1);
@@ -2682,7 +2714,17 @@ cad_status cad_op_conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, c
     return guard([&] {
         require(cin % 4 == 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && xcoff % 4 == 0 && ycoff % 4 == 0,
                 "channels / strides must be multiples of 4");
-        cad::conv3x3_fwd(x, ldx, xcoff, cin, w, cout, y, ldy, ycoff, B, H, W, nullptr, S(stream));
+        // the S3 window kernels' weight twin, built for this call when that path is on
+        void* twin = nullptr;
+        const int bn = cad::conv3x3_wtwin_on() ? cad::conv3x3_wtwin_bn(cin, W, cout) : 0;
+        if (bn) {
+            HIPCHK(hipMallocAsync(&twin, (size_t)cad::conv3x3_wtwin_bytes(cin, cout), S(stream)));
+            cad::WPrepList L{};
+            wprep_twin_add(L, cad::WPREP_WTWIN_FWD, w, twin, cout, cin, bn);
+            cad::weight_prep(L, S(stream));
+        }
+        cad::conv3x3_fwd(x, ldx, xcoff, cin, w, cout, y, ldy, ycoff, B, H, W, nullptr, S(stream), twin);
+        if (twin) HIPCHK(hipFreeAsync(twin, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -2693,7 +2735,16 @@ cad_status cad_op_conv3x3_dgrad(const float* dz, int cout, const float* w, int c
         float* wd = nullptr;
         HIPCHK(hipMallocAsync((void**)&wd, sizeof(float) * (size_t)cout * 9 * cin, S(stream)));
         cad::repack_conv_dgrad(w, wd, cout, cin, S(stream));
-        cad::conv3x3_dgrad(dz, cout, wd, cin, dx, lddx, B, H, W, S(stream));
+        void* twin = nullptr;
+        const int bn = cad::conv3x3_wtwin_on() ? cad::conv3x3_wtwin_bn(cout, W, cin) : 0;
+        if (bn) {
+            HIPCHK(hipMallocAsync(&twin, (size_t)cad::conv3x3_wtwin_bytes(cout, cin), S(stream)));
+            cad::WPrepList L{};
+            wprep_twin_add(L, cad::WPREP_WTWIN_DGRAD, w, twin, cout, cin, bn);
+            cad::weight_prep(L, S(stream));
+        }
+        cad::conv3x3_dgrad(dz, cout, wd, cin, dx, lddx, B, H, W, S(stream), twin);
+        if (twin) HIPCHK(hipFreeAsync(twin, S(stream)));
         HIPCHK(hipFreeAsync(wd, S(stream)));
         HIPCHK(hipGetLastError());
     });

@@ -123,9 +123,10 @@ __global__ __launch_bounds__(256) void k_convT_wgrad_s3(GemmArgs a) { convT_wgra
 
 // window-tiled conv3x3 forward/dgrad (gemm_win.hpp): BM = R*CW output pixels of one image; 128x128
 // tiles (WM = WN = 2) or, for N <= 64, 256x64 (WM = 4, WN = 1)
-template <int R, int CW, class Epi>
+// WT: the weights come from their three-plane twin (a.wtwin) by LDS-DMA
+template <int R, int CW, class Epi, bool WT = false>
 __global__ __launch_bounds__(256, 3) void k_conv3x3_win_s3(GemmArgs a) {
-    conv3x3_win_body<3, R, CW, R * CW == 128 ? 2 : 4, R * CW == 128 ? 2 : 1, Epi>(a);
+    conv3x3_win_body<3, R, CW, R * CW == 128 ? 2 : 4, R * CW == 128 ? 2 : 1, Epi, WT>(a);
 }
 
 // window-tiled conv3x3 forward/dgrad on the pre-split bf16 twins (B1)
@@ -458,9 +459,10 @@ struct WinPick {
     bool n96 = false;   // B1 256 x 96 tiles (k_conv3x3_win_bf16p3)
     int bn() const { return n96 ? 96 : big ? (R * CW == 256 ? 128 : 64) : R * CW == 128 ? 128 : 64; }
 };
-WinPick pick_win(int cin, int W, int N) {
+// (the shape rule alone: what the engine would pick when it is S3)
+WinPick pick_win_shape(int cin, int W, int N) {
     WinPick w;
-    if (engine() != 1 || cin % 16) return w;
+    if (cin % 16) return w;
     const int BM = N <= 64 ? 256 : 128;
     if (N % (BM == 128 ? 128 : 64)) return w;
     static const int c128[] = {64, 32, 16, 8}, c256[] = {128, 64};
@@ -474,6 +476,7 @@ WinPick pick_win(int cin, int W, int N) {
         }
     return w;
 }
+WinPick pick_win(int cin, int W, int N) { return engine() == 1 ? pick_win_shape(cin, W, N) : WinPick{}; }
 int win_blocks(const WinPick& w, int B, int H, int W) { return B * cdiv(H, w.R) * (W / w.CW); }
 // PS = false: S3 window kernel (fp32 operands, in-loader split); true: B1 on the pre-split twins
 template <bool PS, int R, int CW, class Epi, bool BIG = false, bool N96 = false>
@@ -484,13 +487,14 @@ void launch_win1(const GemmArgs& a, hipStream_t st) {
     void (*fn)(GemmArgs);
     if constexpr (N96) fn = k_conv3x3_win_bf16p3<R, CW, Epi>;
     else if constexpr (BIG) fn = k_conv3x3_win_bf16p4<R, CW, Epi, BN == 64>;
-    else fn = PS ? (void (*)(GemmArgs))k_conv3x3_win_bf16p<R, CW, Epi> : (void (*)(GemmArgs))k_conv3x3_win_s3<R, CW, Epi>;
+    else if constexpr (PS) fn = k_conv3x3_win_bf16p<R, CW, Epi>;
+    else fn = a.wtwin ? (void (*)(GemmArgs))k_conv3x3_win_s3<R, CW, Epi, true> : (void (*)(GemmArgs))k_conv3x3_win_s3<R, CW, Epi>;
     if (prof_enabled()) {
         char name[160];
-        snprintf(name, sizeof(name), "void cad::k_conv3x3_win_%s<%d, %d, cad::%s%s>(cad::GemmArgs)",
+        snprintf(name, sizeof(name), "void cad::k_conv3x3_win_%s<%d, %d, cad::%s%s%s>(cad::GemmArgs)",
                  N96 ? "bf16p3" : BIG ? "bf16p4" : PS ? "bf16p" : "s3", R, CW,
                  Epi::STATS ? "EpiStoreStats" : is_bnsums<Epi>::value ? "EpiStoreBnSums" : "EpiStore",
-                 Epi::BF16 ? "B16" : "");
+                 Epi::BF16 ? "B16" : "", !PS && !N96 && !BIG && a.wtwin ? ", true" : "");
         prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
         hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
         prof_pop(st);
@@ -848,10 +852,22 @@ int conv3x3_stats_rows(int cin, int B, int H, int W, int cout, bool ps) {
     return cdiv((int64_t)B * H * W, tile_m(pick_cfg(B * H * W, cout)));
 }
 
+int conv3x3_wtwin_bn(int cin, int W, int N) {
+    const WinPick w = pick_win_shape(cin, W, N);
+    return w.R ? w.bn() : 0;
+}
+int64_t conv3x3_wtwin_bytes(int cin, int N) { return (int64_t)N * 9 * cin * 6; }
+bool conv3x3_wtwin_on() {
+    const char* e = std::getenv("CAD_S3_WTWIN");
+    const bool on = e && e[0] ? std::atoi(e) != 0 : kWtwinDefault;
+    return on && engine() == 1;
+}
+
 void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y,
-                 int64_t ldy, int ycoff, int B, int H, int W, float* stats, hipStream_t st) {
+                 int64_t ldy, int ycoff, int B, int H, int W, float* stats, hipStream_t st, const void* wtwin) {
     CAD_NO_ALIAS("conv3x3_fwd", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, 4, "y")},
-                 {aview(x, (int64_t)B * H * W, ldx, xcoff, cin, 4, "x"), aview(w, cout, 9 * cin, 0, 9 * cin, 4, "w")});
+                 {aview(x, (int64_t)B * H * W, ldx, xcoff, cin, 4, "x"), aview(w, cout, 9 * cin, 0, 9 * cin, 4, "w"),
+                  aview(wtwin, 1, conv3x3_wtwin_bytes(cin, cout), 0, wtwin ? conv3x3_wtwin_bytes(cin, cout) : 0, 1, "wtwin")});
     GemmArgs a{};
     a.M = B * H * W; a.N = cout; a.K = 9 * cin;
     a.B = B; a.H = H; a.W = W;
@@ -860,6 +876,7 @@ void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w
     a.C = y; a.ldc = ldy; a.c_coff = ycoff;
     a.stats = stats;
     if (const WinPick w = pick_win(cin, W, cout); w.R) {
+        a.wtwin = wtwin;
         if (stats) launch_win<EpiStoreStats>(w, a, st);
         else launch_win<EpiStore>(w, a, st);
         return;
@@ -883,9 +900,10 @@ void convT_fwd(const float* x, int64_t ldx, int cin, const float* wf, const floa
 }
 
 void conv3x3_dgrad(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx,
-                   int B, int H, int W, hipStream_t st) {
+                   int B, int H, int W, hipStream_t st, const void* wtwin) {
     CAD_NO_ALIAS("conv3x3_dgrad", {aview(dx, (int64_t)B * H * W, lddx, 0, cin, 4, "dx")},
-                 {aview(dz, (int64_t)B * H * W, cout, 0, cout, 4, "dz"), aview(wd, cin, 9 * cout, 0, 9 * cout, 4, "w")});
+                 {aview(dz, (int64_t)B * H * W, cout, 0, cout, 4, "dz"), aview(wd, cin, 9 * cout, 0, 9 * cout, 4, "w"),
+                  aview(wtwin, 1, conv3x3_wtwin_bytes(cout, cin), 0, wtwin ? conv3x3_wtwin_bytes(cout, cin) : 0, 1, "wtwin")});
     GemmArgs a{};
     a.M = B * H * W; a.N = cin; a.K = 9 * cout;
     a.B = B; a.H = H; a.W = W;
@@ -893,6 +911,7 @@ void conv3x3_dgrad(const float* dz, int cout, const float* wd, int cin, float* d
     a.Bm = wd; a.ldb = 9 * cout;
     a.C = dx; a.ldc = lddx; a.c_coff = 0;
     if (const WinPick w = pick_win(cout, W, cin); w.R) {
+        a.wtwin = wtwin;
         launch_win<EpiStore>(w, a, st);
         return;
     }
@@ -1033,7 +1052,7 @@ int dgrad_bnsums_launch(const WinPick& wp, GemmArgs& a, const BnSums& bn, hipStr
 }  // namespace
 
 int conv3x3_dgrad_bnsums(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx, int B, int H,
-                         int W, const BnSums& bn, hipStream_t st) {
+                         int W, const BnSums& bn, hipStream_t st, const void* wtwin) {
     const WinPick w = pick_win(cout, W, cin);
     if (!w.R || bn.y_bf16) return 0;
     GemmArgs a{};
@@ -1042,6 +1061,7 @@ int conv3x3_dgrad_bnsums(const float* dz, int cout, const float* wd, int cin, fl
     a.A = dz; a.lda = cout; a.a_coff = 0; a.a_cin = cout;
     a.Bm = wd; a.ldb = 9 * cout;
     a.C = dx; a.ldc = lddx; a.c_coff = 0;
+    a.wtwin = wtwin;
     return dgrad_bnsums_launch<false, false>(w, a, bn, st);
 }
 

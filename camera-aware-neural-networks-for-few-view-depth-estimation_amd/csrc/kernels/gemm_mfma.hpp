@@ -69,6 +69,9 @@ struct GemmArgs {
     const float *bn_scale, *bn_shift, *bn_mean, *bn_invstd, *bn_coef;
     const void* bn_g; int64_t bn_ldg;
     double* bn_part;
+    // conv3x3 window kernels on the S3 engine: the weights' three-plane twin in LDS-image order
+    // (gemm_win.hpp WinTwinGeo), or nullptr for the in-loader split of Bm
+    const void* wtwin;
 };
 
 

@@ -15,6 +15,9 @@
 // Per stage and wave: 3 k16 steps x MI x NJ blocks x NP products (S3: 72 MFMAs).  LDS holds ONE
 // stage (A window + B taps; 49.5 KB for BM = BN = 128 on S3, so 3 workgroups per CU), register-staged:
 // the next stage's global loads are in flight during the MFMAs, then barrier / store / barrier.
+// On S3 with a weight twin (WT, a.wtwin: the weights' planes written once per step in this image's
+// order) B is not staged through registers at all: after the barrier the stage's B image is copied by
+// LDS-DMA while A is split and stored (WinTwinGeo below).
 // Requirements (host: conv_kernels.hip pick_win): cin % 16 == 0, W % CW == 0, N % BN == 0; rows past H in the
 // last block row are computed on zeros and not stored.  Accumulation order differs from the im2col
 // kernel (cb-major), so the two agree to rounding, not bit for bit.
@@ -37,6 +40,38 @@ struct WinGeo {
     static constexpr int PLA = WPIX * 16;          // bf16 elements per A plane
     static constexpr int PLB = BN * 16;            // bf16 elements per B plane (one tap)
 };
+
+// One LDS-DMA wave-instruction: buffer_load_dwordx4 ... lds (16 B per lane to M0 + 16 lane).  Issued
+// by inline asm so the compiler's wait-count pass does not see it: otherwise, unable to prove that the
+// fragment reads of the current ring slot do not alias the DMA's destination, it waits vmcnt(0)
+// before them and drains the ring; the kernel counts these loads itself (wgd_wait_barrier).
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+struct DmaRsrc {
+    i32x4_t d;
+};
+__device__ __forceinline__ DmaRsrc dma_rsrc(const void* base) {
+    const uint64_t a = reinterpret_cast<uint64_t>(base);
+    DmaRsrc r;
+    r.d[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+    r.d[1] = __builtin_amdgcn_readfirstlane((int)((uint32_t)(a >> 32) & 0xFFFF));
+    r.d[2] = (int)kRecords;
+    r.d[3] = 0x00020000;
+    return r;
+}
+__device__ __forceinline__ void dma16(const DmaRsrc& r, const void* lds_dst, uint32_t voff) {
+    const uint32_t m0 = __builtin_amdgcn_readfirstlane(
+        (uint32_t)reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)lds_dst));
+    asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r.d), "s"(m0)
+                 : "memory", "m0");
+}
+
+template <int WAITN>
+__device__ __forceinline__ void wgd_wait_barrier() {
+    // the wave's DMAs of the stage about to be read have landed (at most WAITN newer ones pending),
+    // then every wave's: a raw barrier (a __syncthreads fence would drain the in-flight DMAs too)
+    if constexpr (WAITN == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(WAITN) : "memory");
+}
 
 // A: the input window of stage (cb, ky) of the block whose first output pixel is (b, y0, x0)
 template <int R, int CW, int BN>
@@ -374,14 +409,39 @@ __device__ __forceinline__ void win_epilogue16(const GemmArgs& a, const floatx4 
     if constexpr (BNS) bns.template finish<WM, WN>(a, lds, tile_lin, n0);
 }
 
+// The B image of a stage as the weight twin holds it (S3, a.wtwin; host: wtwin_bytes, k_weight_prep
+// WPREP_WTWIN_*): the weights do not change within a step and are the same for every output block, so
+// their three split3 planes are written once per step in this kernel's LDS order — one contiguous
+// block per (N tile, stage (cb, ky)): [tap kx][plane][row][16 k] with the s3_off<16> half swap already
+// applied (the swizzle is on the source side) — and a stage's B is a lane-linear LDS-DMA copy of
+// 9 * BN * 32 bytes: no B staging registers, no split VALU and no ds_write for the weights.
+template <int BN>
+struct WinTwinGeo {
+    static constexpr int STAGE = 9 * BN * 32;        // bytes of one stage's B image
+    static constexpr int NI = STAGE / 1024;          // DMA wave-instructions per stage (36 / 18)
+    static constexpr int SLOTS = (NI + 3) / 4;       // per wave (wave w issues q = w, w + 4, ...)
+};
+// dma16 with the wait state between the M0 write and the LDS-DMA that reads it
+__device__ __forceinline__ void dma16_m0(const DmaRsrc& r, const void* lds_dst, uint32_t voff) {
+    const uint32_t m0 = __builtin_amdgcn_readfirstlane(
+        (uint32_t)reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)lds_dst));
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r.d), "s"(m0)
+                 : "memory", "m0");
+}
+
 // blocks: gridDim.x = B * ceil(H / R) * (W / CW) output blocks (XCD-aware order), gridDim.y = N tiles
-template <int NP, int R, int CW, int WM, int WN, class Epi>
+// WT: B comes from the weight twin by LDS-DMA (above) instead of the in-loader split of a.Bm; the MFMA
+// operands and their order are the same, so the outputs agree bit for bit.
+template <int NP, int R, int CW, int WM, int WN, class Epi, bool WT = false>
 __device__ __forceinline__ void conv3x3_win_body(const GemmArgs& a) {
     constexpr int MI = 2, NJ = 2;
     constexpr int BM = 32 * MI * WM, BN = 32 * NJ * WN;
     static_assert(BM == R * CW, "tile");
+    static_assert(!WT || NP == 3, "weight twin: S3 only");
     using G = WinGeo<R, CW, BN>;
+    using T = WinTwinGeo<BN>;
     constexpr int SA = NP * G::PLA, SB = 3 * NP * G::PLB;   // bf16 elements
+    static_assert(!WT || (SB * 2 == T::STAGE && (SA * 2) % 16 == 0), "twin stage = the B image");
     __shared__ __attribute__((aligned(16))) uint16_t lds[SA + SB];
 
     const int tid = threadIdx.x;
@@ -394,10 +454,14 @@ __device__ __forceinline__ void conv3x3_win_body(const GemmArgs& a) {
     const int cin = a.a_cin;
     const int S = 3 * (cin / 16);   // stages
 
+    // twin path: this N tile's stages, S * STAGE bytes from the descriptor's base (cin <= 2^14)
+    [[maybe_unused]] DmaRsrc rsw;
+    [[maybe_unused]] const int wv = __builtin_amdgcn_readfirstlane(wave);   // (uniform: scalar branches)
+    if constexpr (WT) rsw = dma_rsrc(static_cast<const char*>(a.wtwin) + (int64_t)tile.y * S * T::STAGE);
     WinA<R, CW, BN> la;
-    WinB<R, CW, BN> lb;
+    [[maybe_unused]] WinB<R, CW, BN> lb;
     la.init(a.A, a.lda, a.a_coff, a.H, a.W, b, y0, x0, tid, 0);
-    lb.init(a.Bm, a.ldb, cin, n0, tid, 0);
+    if constexpr (!WT) lb.init(a.Bm, a.ldb, cin, n0, tid, 0);
 
     // window pixel of the lane's A row in each of its MI blocks (tap kx adds kx)
     int wpix[MI];
@@ -410,8 +474,19 @@ __device__ __forceinline__ void conv3x3_win_body(const GemmArgs& a) {
 
     floatx16 acc[MI][NJ];
     acc_zero(acc);
-    float4 ra[G::NVA], rb[G::NVB];
+    float4 ra[G::NVA];
+    [[maybe_unused]] float4 rb[WT ? 1 : G::NVB];
 
+    // the DMAs of stage s's B image (issued by inline asm: the kernel waits for them itself)
+    auto dma_b = [&](int s) {
+        const uint32_t src = (uint32_t)s * T::STAGE + (uint32_t)lane * 16;
+        const char* dst = reinterpret_cast<const char*>(lds + SA);
+#pragma unroll
+        for (int t = 0; t < T::SLOTS; ++t) {
+            const int q = wv + 4 * t;
+            if (T::NI % 4 == 0 || q < T::NI) dma16_m0(rsw, dst + q * 1024, src + (uint32_t)q * 1024);   // wave-uniform
+        }
+    };
     auto store = [&]() {
 #pragma unroll
         for (int j = 0; j < G::NVA; ++j) {
@@ -423,14 +498,16 @@ __device__ __forceinline__ void conv3x3_win_body(const GemmArgs& a) {
                 for (int p = 0; p < NP; ++p) *reinterpret_cast<uint2*>(lds + p * G::PLA + off) = sp.p[p];
             }
         }
+        if constexpr (!WT) {
 #pragma unroll
-        for (int j = 0; j < G::NVB; ++j) {
-            const int f = tid + 256 * j;
-            const int t = f / (BN * 4), rem = f - t * (BN * 4);
-            const auto sp = split_np<NP>(rb[j]);
-            const int off = SA + t * NP * G::PLB + s3_off<16>(rem >> 2, (rem & 3) * 4);
+            for (int j = 0; j < G::NVB; ++j) {
+                const int f = tid + 256 * j;
+                const int t = f / (BN * 4), rem = f - t * (BN * 4);
+                const auto sp = split_np<NP>(rb[j]);
+                const int off = SA + t * NP * G::PLB + s3_off<16>(rem >> 2, (rem & 3) * 4);
 #pragma unroll
-            for (int p = 0; p < NP; ++p) *reinterpret_cast<uint2*>(lds + off + p * G::PLB) = sp.p[p];
+                for (int p = 0; p < NP; ++p) *reinterpret_cast<uint2*>(lds + off + p * G::PLB) = sp.p[p];
+            }
         }
     };
     auto compute = [&]() {
@@ -449,23 +526,56 @@ __device__ __forceinline__ void conv3x3_win_body(const GemmArgs& a) {
         }
     };
 
-    if (S > 0) {
-        la.load(ra);
-        lb.load(rb);
-        store();
-    }
-    __syncthreads();
-    for (int s = 0; s < S; ++s) {
-        const bool more = s + 1 < S;
-        if (more) {
+    if constexpr (WT) {
+        // A(s + 1) into registers; compute(s); barrier; B(s + 1) DMAs into the (free) image; split and
+        // store A(s + 1) while they fly; wait for the DMAs; barrier.  The compiler does not count the
+        // DMAs: A's registers are made complete before the DMAs are issued (the empty asm uses them), so
+        // the wait hipcc places for A's loads does not also wait for the DMAs behind them.
+        auto a_landed = [&]() {
+#pragma unroll
+            for (int j = 0; j < G::NVA; ++j)
+                asm volatile("" : "+v"(ra[j].x), "+v"(ra[j].y), "+v"(ra[j].z), "+v"(ra[j].w));
+        };
+        if (S > 0) {
+            la.load(ra);
+            a_landed();
+            dma_b(0);
+            store();
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        for (int s = 0; s < S; ++s) {
+            const bool more = s + 1 < S;
+            if (more) la.load(ra);
+            compute();
+            __syncthreads();
+            if (more) {
+                a_landed();
+                dma_b(s + 1);
+                store();
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+        }
+    } else {
+        if (S > 0) {
             la.load(ra);
             lb.load(rb);
-        }
-        compute();
-        __syncthreads();
-        if (more) {
             store();
+        }
+        __syncthreads();
+        for (int s = 0; s < S; ++s) {
+            const bool more = s + 1 < S;
+            if (more) {
+                la.load(ra);
+                lb.load(rb);
+            }
+            compute();
             __syncthreads();
+            if (more) {
+                store();
+                __syncthreads();
+            }
         }
     }
     win_epilogue<WM, WN, MI, NJ, CW, Epi>(a, acc, tile.x, n0, b, y0, x0, reinterpret_cast<float*>(lds));
@@ -1218,38 +1328,6 @@ struct WgdGeo {
     static constexpr int SA = P * 128, SB = NIB * 8 * 128, STAGE = SA + SB;
     static constexpr int NBUF = NBUF_;   // 3: two stages in flight; 2: one (half the LDS)
 };
-
-// One LDS-DMA wave-instruction: buffer_load_dwordx4 ... lds (16 B per lane to M0 + 16 lane).  Issued
-// by inline asm so the compiler's wait-count pass does not see it: otherwise, unable to prove that the
-// fragment reads of the current ring slot do not alias the DMA's destination, it waits vmcnt(0)
-// before them and drains the ring; the kernel counts these loads itself (wgd_wait_barrier).
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-struct DmaRsrc {
-    i32x4_t d;
-};
-__device__ __forceinline__ DmaRsrc dma_rsrc(const void* base) {
-    const uint64_t a = reinterpret_cast<uint64_t>(base);
-    DmaRsrc r;
-    r.d[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-    r.d[1] = __builtin_amdgcn_readfirstlane((int)((uint32_t)(a >> 32) & 0xFFFF));
-    r.d[2] = (int)kRecords;
-    r.d[3] = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ void dma16(const DmaRsrc& r, const void* lds_dst, uint32_t voff) {
-    const uint32_t m0 = __builtin_amdgcn_readfirstlane(
-        (uint32_t)reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)lds_dst));
-    asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r.d), "s"(m0)
-                 : "memory", "m0");
-}
-
-template <int WAITN>
-__device__ __forceinline__ void wgd_wait_barrier() {
-    // the wave's DMAs of the stage about to be read have landed (at most WAITN newer ones pending),
-    // then every wave's: a raw barrier (a __syncthreads fence would drain the in-flight DMAs too)
-    if constexpr (WAITN == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(WAITN) : "memory");
-}
 
 template <int P, int NBUF = 3>
 __device__ __forceinline__ void conv3x3_wgrad_win_dma_body(const GemmArgs& a) {

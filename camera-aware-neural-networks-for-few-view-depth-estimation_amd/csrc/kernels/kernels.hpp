@@ -50,13 +50,28 @@ void alias_check_impl(const char* op, std::initializer_list<AliasView> outs, std
 void set_gemm_engine(int e);
 int gemm_engine();
 // y = conv3x3(x) (+ per-tile BN partials [rows][2][cout] when stats != nullptr)
+// wtwin (here and in conv3x3_dgrad / conv3x3_dgrad_bnsums): the weights' three-plane twin (below), read
+// by the S3 window kernels instead of splitting w in their loaders; nullptr, or a shape the window
+// kernels do not serve: the in-loader split.  Same bits either way.
 void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y,
-                 int64_t ldy, int ycoff, int B, int H, int W, float* stats, hipStream_t st);
+                 int64_t ldy, int ycoff, int B, int H, int W, float* stats, hipStream_t st, const void* wtwin = nullptr);
+// Weight twin of a 3 x 3 convolution for the S3 window kernels: the three bf16 planes of split3 of
+// Wt[n][tap * cin + ci] (forward: n = cout, the OHWI parameters; dgrad: the repack, n and cin swapped) in
+// the kernels' LDS-image order, one 9 * bn * 32-byte block per (N tile of bn rows, stage (cb, ky)):
+// [tap kx][plane][row][16 k], halves swapped as s3_off<16> does.  Written by weight_prep
+// (WPREP_WTWIN_FWD / _DGRAD).  conv3x3_wtwin_bn: the tile width bn the window kernels use for (cin, W, N)
+// on the S3 engine, 0 where they do not run (whatever the current engine); conv3x3_wtwin_bytes: 6 per weight.
+// conv3x3_wtwin_on: the S3 engine is selected and CAD_S3_WTWIN (read per call; default kWtwinDefault)
+// does not turn the twin path off.
+constexpr bool kWtwinDefault = true;
+int conv3x3_wtwin_bn(int cin, int W, int N);
+int64_t conv3x3_wtwin_bytes(int cin, int N);
+bool conv3x3_wtwin_on();
 // BN partial rows of conv3x3_fwd (ps = true: of conv3x3_fwd_ps on the pre-split twins)
 int conv3x3_stats_rows(int cin, int B, int H, int W, int cout, bool ps = false);
 // dx[pix][ci] = conv3x3(dz, wd) with wd = repacked [ci][tap'][co]
 void conv3x3_dgrad(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx,
-                   int B, int H, int W, hipStream_t st);
+                   int B, int H, int W, hipStream_t st, const void* wtwin = nullptr);
 // dw[co][tap][ci] = sum_pix dz[pix][co] * im2col(x)[pix][tap,ci]
 void conv3x3_wgrad(const float* dz, int cout, const float* x, int64_t ldx, int xcoff, int cin, float* dw,
                    int B, int H, int W, float* slab, int64_t slab_cap, hipStream_t st);
@@ -275,7 +290,7 @@ struct BnSums {
 // conv3x3 input gradient (S3 engine, fp32 dx) whose window epilogue also forms bn's backward sums over
 // dx: returns the tile count (0 = not available for this shape: nothing launched)
 int conv3x3_dgrad_bnsums(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx, int B, int H,
-                         int W, const BnSums& bn, hipStream_t st);
+                         int W, const BnSums& bn, hipStream_t st, const void* wtwin = nullptr);
 // an encoder block's bn2 + ReLU fused with the next level's MaxPool2d(2): writes the block output
 // (fp32 rows `out` (ldo) and/or its 1-plane twin `os` (ldos), channel offset 0) and the pooled output
 // (fp32 `pool` and/or its twin `pool_split`, dense ld C) with the argmax codes, exactly what
@@ -369,17 +384,21 @@ void repack_convT_fwd(const float* wm, float* wf, int cin, int cout, hipStream_t
 // WPREP_DGRAD  OHWI [co][tap][ci] -> [ci][8 - tap][co] (repack_conv_dgrad);
 // WPREP_CONVT  [ci][q][co] -> [q][co][ci] (repack_convT_fwd);
 // WPREP_TRANSPOSE [cout][cin] -> [cin][cout] (transpose_split: N = cout rows of K = cin).
+// WPREP_WTWIN_FWD / WPREP_WTWIN_DGRAD: OHWI [co][tap][ci] -> the S3 window kernels' weight twin (d16;
+// conv3x3_wtwin_* above) of the forward (rows = cout) or of the dgrad repack (rows = cin), tile width bn;
+// the planes are split3's bits.
 // n = elements, a multiple of 8.
-enum { WPREP_SPLIT = 0, WPREP_DGRAD = 1, WPREP_CONVT = 2, WPREP_TRANSPOSE = 3 };
+enum { WPREP_SPLIT = 0, WPREP_DGRAD = 1, WPREP_CONVT = 2, WPREP_TRANSPOSE = 3, WPREP_WTWIN_FWD = 4, WPREP_WTWIN_DGRAD = 5 };
 struct WPrepJob {
     const float* src;
     float* d32;
     void* d16;
     int kind, cout, cin;
     int blk0;   // first block of this job (filled by weight_prep)
+    int bn;     // WPREP_WTWIN_*: rows per N tile
     int64_t n;
 };
-constexpr int kWPrepMaxJobs = 24;
+constexpr int kWPrepMaxJobs = 40;
 struct WPrepList {
     WPrepJob job[kWPrepMaxJobs];
     int njobs;

@@ -1260,6 +1260,42 @@ __global__ __launch_bounds__(256) void k_weight_prep(WPrepList list) {
     const WPrepJob& jb = list.job[j];
     const int64_t i = ((int64_t)(blockIdx.x - jb.blk0) * 256 + threadIdx.x) * 8;
     if (i >= jb.n) return;
+    if (jb.kind == WPREP_WTWIN_FWD || jb.kind == WPREP_WTWIN_DGRAD) {
+        // Weight twin of the S3 window kernels (gemm_win.hpp WinTwinGeo).  Wt[n][tap * kc + k]: forward
+        // n = co, k = ci (kc = cin); dgrad n = ci, k = co (kc = cout), Wt = w[co][8 - tap][ci].  Thread o = i / 8
+        // owns the 8 k of one 16-B LDS chunk, o = (((nt * S + s) * 3 + kx) * bn + row) * 2 + hs in image
+        // order: hs is the chunk's place in its 32-B row, which holds k-half hs ^ ((row >> 3) & 1).
+        const bool fwd = jb.kind == WPREP_WTWIN_FWD;
+        const int kc = fwd ? jb.cin : jb.cout, bn = jb.bn;
+        const int S = 3 * (kc / 16);
+        int64_t o = i >> 3;
+        const int hs = (int)(o & 1); o >>= 1;
+        const int row = (int)(o % bn); o /= bn;
+        const int kx = (int)(o % 3); o /= 3;
+        const int s = (int)(o % S);
+        const int nt = (int)(o / S);
+        const int cb = s / 3, ky = s - 3 * cb;
+        const int n = nt * bn + row, tap = 3 * ky + kx;
+        const int k0 = cb * 16 + ((hs ^ ((row >> 3) & 1)) << 3);
+        float4 v0, v1;
+        if (fwd) {
+            const float* p = jb.src + ((int64_t)n * 9 + tap) * jb.cin + k0;
+            v0 = *reinterpret_cast<const float4*>(p);
+            v1 = *reinterpret_cast<const float4*>(p + 4);
+        } else {
+            float t[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) t[e] = jb.src[((int64_t)(k0 + e) * 9 + (8 - tap)) * jb.cin + n];
+            v0 = make_float4(t[0], t[1], t[2], t[3]);
+            v1 = make_float4(t[4], t[5], t[6], t[7]);
+        }
+        const Split4 sa = split3(v0), sb = split3(v1);
+        char* dst = static_cast<char*>(jb.d16) + ((int64_t)nt * S + s) * (9 * bn * 32) + (kx * 3 * bn + row) * 32 + hs * 16;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+            *reinterpret_cast<uint4*>(dst + p * bn * 32) = make_uint4(sa.p[p].x, sa.p[p].y, sb.p[p].x, sb.p[p].y);
+        return;
+    }
     const int ne = (int)min<int64_t>(8, jb.n - i);
     float v[8];
 #pragma unroll
@@ -1303,6 +1339,11 @@ void weight_prep(WPrepList& list, hipStream_t st) {
     for (int j = 0; j < list.njobs; ++j) {
         WPrepJob& jb = list.job[j];
         if (jb.d16 && jb.n % 8) throw std::runtime_error("weight_prep: bf16 twin size not a multiple of 8");
+        if (jb.kind == WPREP_WTWIN_FWD || jb.kind == WPREP_WTWIN_DGRAD) {
+            const int rows = jb.kind == WPREP_WTWIN_FWD ? jb.cout : jb.cin, kc = jb.kind == WPREP_WTWIN_FWD ? jb.cin : jb.cout;
+            if (!jb.d16 || jb.d32 || jb.bn <= 0 || rows % jb.bn || kc % 16 || jb.n != (int64_t)jb.cout * 9 * jb.cin)
+                throw std::runtime_error("weight_prep: weight twin job does not match the window kernels' tiles");
+        }
         jb.blk0 = blocks;
         blocks += (int)cdiv(cdiv(jb.n, 8), (int64_t)256);
     }
