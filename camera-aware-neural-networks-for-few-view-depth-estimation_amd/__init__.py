@@ -16,7 +16,8 @@ def __getattr__(name):
     if name in ("BaselineUNet", "IntrinsicsConditionedUNet", "IntrinsicsAttentionUNet", "RayConditionedUNet", "CombinedDepthLoss", "Adam",
                 "Trainer", "Communicator", "save", "load", "clip_grad_norm_", "depth_metrics", "ray_directions", "camera_from_K",
                 "ResNetUNet", "GeometryAwareNetwork", "LightweightGeometryNetwork", "depth_metrics_full", "Evaluator",
-                "evaluate", "EVAL_KEYS", "valid_medians", "Optimizer", "eval_strata_finish", "strata_angle_thresholds"):
+                "evaluate", "EVAL_KEYS", "valid_medians", "Optimizer", "eval_strata_finish", "strata_angle_thresholds",
+                "eval_geom_finish", "depth_normals", "GEOM_KEYS"):
         from . import model
         return getattr(model, name)
     if name == "lr_at":

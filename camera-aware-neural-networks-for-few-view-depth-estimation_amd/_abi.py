@@ -92,6 +92,17 @@ class EvalSummary(C.Structure):
     _fields_ = [("count", I64)] + [(k, F * 12) for k in ("mean", "std", "median", "min", "max", "pooled")]
 
 
+GEOM_SUMS = 8      # CAD_GEOM_SUMS
+GEOM_KEYS = ["normal_mean", "normal_median", "normal_rmse", "normal_11.25", "normal_22.5", "normal_30",
+             "num_normal_pixels", "point_mae", "point_rmse"]   # cad.h's CAD_GEOM_METRICS order
+
+
+class GeomSummary(C.Structure):
+    """cad_geom_summary (cad.h)."""
+    _fields_ = [("count", I64), ("count_normal", I64), ("count_point", I64)] + \
+               [(k, F * 9) for k in ("mean", "std", "median", "min", "max", "pooled")]
+
+
 STRATA_MAX_BINS = 16                    # CAD_STRATA_MAX_BINS
 STRATA_AXES = {"depth": 0, "angle": 1}  # CAD_STRATA_DEPTH / CAD_STRATA_ANGLE
 
@@ -271,6 +282,12 @@ SIGNATURES = {
     "cad_evaluator_strata_sums": (I, [P, I, C.POINTER(C.c_double), P]),
     "cad_strata_angle_thresholds": (I, [FP, I, FP]),
     "cad_eval_strata_finish": (I, [C.POINTER(C.c_double), I64, I, FP, C.POINTER(EvalSummary)]),
+    "cad_evaluator_set_geometry": (I, [P, I]),
+    "cad_evaluator_get_geometry": (I, [P]),
+    "cad_evaluator_geom_sums": (I, [P, C.POINTER(C.c_double), P]),
+    "cad_evaluator_geom_medians": (I, [P, FP, P]),
+    "cad_eval_geom_finish": (I, [C.POINTER(C.c_double), FP, C.POINTER(C.c_double), I64, FP, C.POINTER(GeomSummary)]),
+    "cad_depth_normals": (I, [P, P, P, I, I, I, F, F, P, P, P]),
     "cad_evaluator_set_alignment": (I, [P, I]),
     "cad_evaluator_get_alignment": (I, [P]),
     "cad_evaluator_alignment": (I, [P, FP, P]),
@@ -348,6 +365,7 @@ SIGNATURES = {
     "cad_exporter_range": (I, [P, P, P, P, I, P, P]),
     "cad_exporter_render": (I, [P, P, P, P, I, C.POINTER(RenderOpts), P, P, P]),
     "cad_exporter_image": (I, [P, P, I, C.POINTER(RenderOpts), P, P]),
+    "cad_exporter_normals": (I, [P, P, P, P, I, C.POINTER(RenderOpts), P, P]),
     "cad_exporter_points": (I, [P, P, P, P, P, I, I, F, F, P, P, P]),
     "cad_hflip": (I, [P, P, I64, I, I, P]),
     "cad_flip_mean": (I, [P, P, P, I64, I, I, P]),

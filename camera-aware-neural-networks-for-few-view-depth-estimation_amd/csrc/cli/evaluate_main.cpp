@@ -5,7 +5,7 @@
 //   build/evaluate -c <final_model.pt | .cadckpt> -g <train_config.yaml> [-o results/eval] [--data-dir D]
 //                  [--split val|train] [--save-predictions] [--gpu 0] [--dry-run]
 //                  [--align none|median|log_mean|scale_shift]
-//                  [--depth-bins 1,2,3,5] [--angle-bins 10,20,30] [--by-sensor]
+//                  [--depth-bins 1,2,3,5] [--angle-bins 10,20,30] [--by-sensor] [--geometry]
 //   build/evaluate --compare A/per_sample.csv B/per_sample.csv [--metric abs_rel] [--seed 42]
 //   build/evaluate --compare A/per_sample_strata.csv B/per_sample_strata.csv --stratum depth:2 [--metric abs_rel]
 //
@@ -26,6 +26,10 @@
 // (long form: index, axis, bin, the twelve metrics; rows without a valid pixel are left out) and a report
 // section per axis; --by-sensor adds strata_sensor.csv (the per-sample rows grouped by the manifest's
 // sensor_type) and a trailing sensor column in per_sample.csv.  Without these options every file is as before.
+// --geometry (cad.h "geometric evaluation") adds summary_geometry.csv (one row per statistic over the nine
+// geometry columns), per_sample_geometry.csv (index, the nine metrics; --compare reads it like per_sample.csv)
+// and a "Geometric metrics" report section: the surface-normal angular error and the 3-D point error of the
+// aligned, clamped prediction, from each sample's K.  The strata files are unaffected by it.
 // --compare with --stratum axis:bin pairs the samples present in that stratum in both long-form files.  Any
 // exception prints "Error: <what>" and exits 1, like build/train.
 #include <algorithm>
@@ -66,7 +70,7 @@ struct Args {
     std::vector<std::string> compare;
     int gpu = 0;
     uint32_t seed = 42;
-    bool save_predictions = false, dry_run = false, by_sensor = false;
+    bool save_predictions = false, dry_run = false, by_sensor = false, geometry = false;
     std::vector<float> depth_bins, angle_bins;   // cuts; empty: the option was not given
     std::string stratum;                         // --compare: "depth:2"
 };
@@ -86,6 +90,8 @@ void usage() {
                  "      --depth-bins arg  Ascending depth cuts in metres, e.g. 1,2,3,5: metrics per depth range\n"
                  "      --angle-bins arg  Ascending cuts in degrees off the optical axis, e.g. 10,20,30\n"
                  "      --by-sensor       Metrics per manifest sensor_type\n"
+                 "      --geometry        Surface-normal angular error and 3-D point error from each sample's K\n"
+                 "                        (over the whole image: per-stratum geometry is not computed)\n"
                  "      --compare A B     Paired comparison of two per_sample.csv files (no GPU use)\n"
                  "      --stratum arg     With --compare on two per_sample_strata.csv files: axis:bin, e.g. depth:2\n"
                  "      --metric arg      Column compared by --compare (default: abs_rel)\n"
@@ -155,6 +161,7 @@ Args parse_args(int argc, char** argv) {
         } else if (k == "--depth-bins") a.depth_bins = parse_cuts(k, next());
         else if (k == "--angle-bins") a.angle_bins = parse_cuts(k, next());
         else if (k == "--by-sensor") a.by_sensor = true;
+        else if (k == "--geometry") a.geometry = true;
         else if (k == "--stratum") a.stratum = next();
         else if (k == "--metric") a.metric = next();
         else if (k == "--seed") a.seed = (uint32_t)std::stoul(next());
@@ -178,11 +185,13 @@ Column read_column(const std::string& path, const std::string& metric) {
     std::string line, cell;
     if (!std::getline(f, line)) throw std::runtime_error(path + " is empty");
     int col = -1, n = 0;
+    std::string names;
     for (std::stringstream hs(line); std::getline(hs, cell, ','); ++n) {
         if (n == 0 && cell != "index") throw std::runtime_error(path + ": the first column must be index");
         if (cell == metric) col = n;
+        if (n >= 1) names += (n > 1 ? ", " : "") + cell;
     }
-    if (col < 1) throw std::runtime_error(path + " has no column '" + metric + "'");
+    if (col < 1) throw std::runtime_error(path + " has no column '" + metric + "' (its columns: " + names + ")");
     Column c;
     while (std::getline(f, line)) {
         if (line.empty()) continue;
@@ -203,13 +212,15 @@ Column read_stratum_column(const std::string& path, const std::string& metric, c
     std::string line, cell;
     if (!std::getline(f, line)) throw std::runtime_error(path + " is empty");
     int col = -1, n = 0;
+    std::string names;
     for (std::stringstream hs(line); std::getline(hs, cell, ','); ++n) {
         static const char* head[3] = {"index", "axis", "bin"};
         if (n < 3 && cell != head[n])
             throw std::runtime_error(path + ": the first columns must be index,axis,bin (a per_sample_strata.csv file)");
         if (n >= 3 && cell == metric) col = n;
+        if (n >= 3) names += (n > 3 ? ", " : "") + cell;
     }
-    if (col < 3) throw std::runtime_error(path + " has no column '" + metric + "'");
+    if (col < 3) throw std::runtime_error(path + " has no column '" + metric + "' (its columns: " + names + ")");
     Column c;
     while (std::getline(f, line)) {
         if (line.empty()) continue;
@@ -349,6 +360,54 @@ void report_strata(std::ostream& rep, const std::string& rule, const char* title
     rep << "\n";
 }
 
+// --geometry: summary_geometry.csv, per_sample_geometry.csv and the report section
+void write_geometry(const Args& a, const GeometryResult& g, std::ostream& rep, const std::string& rule) {
+    const auto& keys = geometryKeys();
+    const size_t n = g.medians.size();
+    {
+        std::ofstream f(a.output + "/per_sample_geometry.csv");
+        if (!f) throw std::runtime_error("cannot write " + a.output + "/per_sample_geometry.csv");
+        f << "index";
+        for (const char* k : keys) f << "," << k;
+        f << "\n" << std::setprecision(9);
+        for (size_t i = 0; i < n; ++i) {
+            f << i;
+            for (int k = 0; k < CAD_GEOM_METRICS; ++k) f << "," << g.per_sample[i * CAD_GEOM_METRICS + (size_t)k];
+            f << "\n";
+        }
+    }
+    const cad_geom_summary& s = g.summary;
+    {
+        std::ofstream f(a.output + "/summary_geometry.csv");
+        if (!f) throw std::runtime_error("cannot write " + a.output + "/summary_geometry.csv");
+        f << "statistic";
+        for (const char* k : keys) f << "," << k;
+        f << "\n" << std::setprecision(9);
+        const std::pair<const char*, const float*> rows[] = {{"mean", s.mean}, {"std", s.std}, {"median", s.median},
+                                                             {"min", s.min},   {"max", s.max}, {"pooled", s.pooled}};
+        for (const auto& row : rows) {
+            f << row.first;
+            for (int k = 0; k < CAD_GEOM_METRICS; ++k) {
+                f << ",";
+                if (!std::isnan(row.second[k])) f << row.second[k];   // the pooled median is not defined: empty
+            }
+            f << "\n";
+        }
+    }
+    rep << rule << "\n                     Geometric Metrics\n" << rule << "\n\n";
+    rep << std::fixed << std::setprecision(4);
+    rep << "Surface normals (degrees, " << s.count_normal << " of " << s.count << " samples with a normal-valid pixel):\n";
+    rep << "  Mean:      " << s.mean[0] << " ± " << s.std[0] << "\n";
+    rep << "  Median:    " << s.mean[1] << " ± " << s.std[1] << "\n";
+    rep << "  RMSE:      " << s.mean[2] << " ± " << s.std[2] << "\n";
+    rep << "  < 11.25°:  " << s.mean[3] << " ± " << s.std[3] << "\n";
+    rep << "  < 22.5°:   " << s.mean[4] << " ± " << s.std[4] << "\n";
+    rep << "  < 30°:     " << s.mean[5] << " ± " << s.std[5] << "\n";
+    rep << "3-D points (metres, " << s.count_point << " of " << s.count << " samples with a valid pixel):\n";
+    rep << "  MAE:       " << s.mean[7] << " ± " << s.std[7] << "\n";
+    rep << "  RMSE:      " << s.mean[8] << " ± " << s.std[8] << "\n\n";
+}
+
 void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
     const auto& keys = metricKeys();
     const bool al = a.align != Alignment::None;
@@ -463,6 +522,7 @@ void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
                     f << "\n";
                 }
     }
+    if (r.geometry.on) write_geometry(a, r.geometry, rep, rule);
     rep << bar << "\n";
 }
 
@@ -511,6 +571,7 @@ int run(const Args& a) {
         list("depth_bins", a.depth_bins);
         list("angle_bins", a.angle_bins);
         if (a.by_sensor) std::cout << ", \"by_sensor\": true";
+        if (a.geometry) std::cout << ", \"geometry\": true";
         std::cout << "}" << std::endl;
         return 0;
     }
@@ -538,6 +599,7 @@ int run(const Args& a) {
     ec.depth_cuts = a.depth_bins;
     ec.angle_cuts_deg = a.angle_bins;
     ec.by_sensor = a.by_sensor;
+    ec.geometry = a.geometry;
     if (a.save_predictions)
         ec.on_batch = [&](int64_t first, const DeviceTensor& pred, int n) {
             const std::vector<float> h = pred.to_host();

@@ -6,18 +6,19 @@
 //   build/predict -c <final_model.pt | .cadckpt> -g <train_config.yaml> [-o results/predict]
 //      -i img.jpg [img2.png ...] [--intrinsics fx,fy,cx,cy | --intrinsics-file intrinsics.txt]
 //    | --split val|train --indices 0,3,7 [--data-dir D]
-//      [--depth-png] [--color-png] [--ply] [--ply-stride S] [--npy] [--panel]
+//      [--depth-png] [--color-png] [--ply] [--ply-stride S] [--npy] [--panel] [--normals]
 //      [--colormap jet|hot|gray] [--range lo,hi] [--flip-tta] [--gpu N] [--dry-run]
 //
 // The model and the dataset come from the training YAML, the keys and code paths of build/evaluate.  File
 // inputs are decoded on the host (JPEG or PNG), uploaded as uint8 and resized to the model's H x W by the
 // device batcher, which scales K with them (--intrinsics is given for the file's own resolution; an
 // intrinsics file holds the nine values of K, row-major); outputs are at the model's resolution and the
-// PLY uses the scaled K.  Conditioned and geometry models, and --ply, need intrinsics.  Dataset samples carry
+// PLY and the normals use the scaled K.  Conditioned and geometry models, --ply and --normals need intrinsics.  Dataset samples carry
 // ground truth: --panel writes rgb | gt | pred | |pred - gt|, gt and pred in gt's range, the error pane in
 // its own range with the hot table, every pane rendered on the device into one buffer.
 // Per image: <stem>_depth.png (16-bit, millimetres), <stem>_color.png, <stem>.ply, <stem>.npy,
-// <stem>_panel.png; predictions.csv holds name, height, width, min, max, points, forward_ms.  Without an
+// <stem>_panel.png, <stem>_normal.png (the predicted surface normals from the depth and K, cad.h
+// cad_exporter_normals: a wall facing the camera is (128, 128, 255)); predictions.csv holds name, height, width, min, max, points, forward_ms.  Without an
 // output flag the depth and colour PNGs are written.  --flip-tta averages the prediction with the mirrored
 // prediction of the mirrored image (K' = K with cx' = W - 1 - cx).  Any exception prints "Error: <what>" and
 // exits 1, like build/train.
@@ -50,7 +51,7 @@ struct Args {
     std::vector<std::string> inputs;
     std::vector<int64_t> indices;
     std::vector<float> intrinsics, range;   // fx, fy, cx, cy; lo, hi
-    bool depth_png = false, color_png = false, ply = false, npy = false, panel = false, flip_tta = false, dry_run = false;
+    bool depth_png = false, color_png = false, ply = false, npy = false, panel = false, normals = false, flip_tta = false, dry_run = false;
     int ply_stride = 1, gpu = 0;
 };
 
@@ -71,6 +72,7 @@ void usage() {
                  "      --ply-stride arg  Keep every S-th pixel of every S-th row (default: 1)\n"
                  "      --npy             Raw fp32 depth\n"
                  "      --panel           rgb | gt | pred | error strip (dataset samples)\n"
+                 "      --normals         Surface-normal PNG from the predicted depth and K (needs intrinsics)\n"
                  "      --colormap arg    jet, hot or gray (default: jet)\n"
                  "      --range lo,hi     Fixed range of the colourised PNG (default: each image's own)\n"
                  "      --flip-tta        Average with the mirrored prediction of the mirrored image\n"
@@ -125,6 +127,7 @@ Args parse_args(int argc, char** argv) {
         else if (k == "--ply-stride") a.ply_stride = std::stoi(next());
         else if (k == "--npy") a.npy = true;
         else if (k == "--panel") a.panel = true;
+        else if (k == "--normals") a.normals = true;
         else if (k == "--colormap") a.colormap = next();
         else if (k == "--range") a.range = split_numbers<float>(next(), "--range");
         else if (k == "--flip-tta") a.flip_tta = true;
@@ -222,7 +225,7 @@ int run(Args a) {
     if (a.ply_stride < 1) throw std::runtime_error("--ply-stride must be at least 1");
     const bool files = !a.inputs.empty();
     if (files == !a.split.empty()) throw std::runtime_error("give either input files (-i) or --split with --indices");
-    if (!(a.depth_png || a.color_png || a.ply || a.npy || a.panel)) a.depth_png = a.color_png = true;
+    if (!(a.depth_png || a.color_png || a.ply || a.npy || a.panel || a.normals)) a.depth_png = a.color_png = true;
 
     bool have_K = false;
     float Kfile[9] = {0, 0, 0, 0, 0, 0, 0, 0, 1};
@@ -248,6 +251,8 @@ int run(Args a) {
         if (!have_K && (geo || c.architecture != "baseline_unet"))
             throw std::runtime_error("model " + c.architecture + " is conditioned on the camera: give --intrinsics fx,fy,cx,cy or --intrinsics-file");
         if (!have_K && a.ply) throw std::runtime_error("--ply needs the camera: give --intrinsics fx,fy,cx,cy or --intrinsics-file");
+        if (!have_K && a.normals)
+            throw std::runtime_error("--normals needs the camera: give --intrinsics fx,fy,cx,cy or --intrinsics-file");
         if (a.panel) throw std::runtime_error("--panel compares with ground truth: use --split and --indices");
     } else {
         if (a.split != "val" && a.split != "train") throw std::runtime_error("--split '" + a.split + "': expected val or train");
@@ -271,7 +276,7 @@ int run(Args a) {
     }
     std::vector<std::string> outputs;
     for (const auto& kv : {std::make_pair(a.depth_png, "depth_png"), std::make_pair(a.color_png, "color_png"), std::make_pair(a.ply, "ply"),
-                           std::make_pair(a.npy, "npy"), std::make_pair(a.panel, "panel")})
+                           std::make_pair(a.npy, "npy"), std::make_pair(a.panel, "panel"), std::make_pair(a.normals, "normals")})
         if (kv.first) outputs.push_back(kv.second);
     const int64_t n_in = files ? (int64_t)a.inputs.size() : (int64_t)a.indices.size();
     if (a.dry_run) {
@@ -343,7 +348,8 @@ int run(Args a) {
     cad::Exporter ex(B, H, W, dev);
     const int64_t cap = ex.point_capacity(a.ply_stride);
     DevBuf range_d(dev, sizeof(float) * 2 * B), u16_d(dev, a.depth_png ? 2 * B * HW : 0), color_d(dev, a.color_png ? 3 * B * HW : 0),
-        panel_d(dev, a.panel ? 12 * B * HW : 0), rec_d(dev, a.ply ? 16 * B * cap : 0), cnt_d(dev, sizeof(int32_t) * B);
+        panel_d(dev, a.panel ? 12 * B * HW : 0), rec_d(dev, a.ply ? 16 * B * cap : 0), cnt_d(dev, sizeof(int32_t) * B),
+        normal_d(dev, a.normals ? 3 * B * HW : 0);
     cad_event *t0 = nullptr, *t1 = nullptr;
     cad::check(cad_event_create(&t0), "event");
     cad::check(cad_event_create(&t1), "event");
@@ -371,6 +377,7 @@ int run(Args a) {
         if (a.depth_png) ex.depth16(pred.data, n, u16_d.as<uint16_t>());
         if (a.color_png) ex.color(pred.data, nullptr, n, cmap, cad::Exporter::Pane{color_d.as<uint8_t>(), 0, 0}, a.range.empty() ? nullptr : a.range.data());
         if (a.ply) ex.points(pred.data, K.data, rgb.data, n, a.ply_stride, 0.1f, c.max_depth, rec_d.p, cnt_d.as<int32_t>());
+        if (a.normals) ex.normals(pred.data, K.data, n, cad::Exporter::Pane{normal_d.as<uint8_t>(), 0, 0});
         if (a.panel) ex.comparison_panel(rgb.data, gt.data, pred.data, n, cmap, panel_d.as<uint8_t>());   // createComparisonViz
         float ms = 0.f;
         cad::check(cad_event_elapsed_ms(t0, t1, &ms), "event");
@@ -388,6 +395,7 @@ int run(Args a) {
             if (a.depth_png) write_png(stem + "_depth.png", u16_d.host<uint16_t>(HW, i * HW).data(), H, W, 1, 16);
             if (a.color_png) write_png(stem + "_color.png", color_d.host<uint8_t>(3 * HW, 3 * i * HW).data(), H, W, 3, 8);
             if (a.panel) write_png(stem + "_panel.png", panel_d.host<uint8_t>(12 * HW, 12 * i * HW).data(), H, 4 * W, 3, 8);
+            if (a.normals) write_png(stem + "_normal.png", normal_d.host<uint8_t>(3 * HW, 3 * i * HW).data(), H, W, 3, 8);
             if (a.npy) write_npy(stem + ".npy", ph.data() + (size_t)i * HW, H, W);
             if (a.ply) {
                 const std::vector<uint8_t> rec = rec_d.host<uint8_t>(16 * (int64_t)counts[(size_t)i], 16 * i * cap);

@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <limits>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -2126,6 +2127,15 @@ struct cad_evaluator {
     int strata_alloc_bins = 0;         // total bins the allocation was made for
     double* strata_table = nullptr;    // [capacity][nbt][12], depth bins first
     double* strata_part = nullptr;     // [Bmax][nb][nbt][12]
+    // geometric evaluation (cad_evaluator_set_geometry): one allocation, made when first turned on
+    int H = 0, geom = 0, geom_nb = 1;
+    void* geom_mem = nullptr;
+    double* geom_table = nullptr;      // [capacity][8]
+    double* geom_part = nullptr;       // [Bmax][geom_nb][8]
+    float* geom_med = nullptr;         // [capacity][2] {median theta, the select's gt median}
+    float* geom_theta = nullptr;       // [Bmax][H*W]
+    uint8_t* geom_valid = nullptr;     // [Bmax][H*W]
+    cad::EvalAlignWs geom_ws{};        // the select's workspace
 };
 
 namespace {
@@ -2172,7 +2182,7 @@ cad_status cad_evaluator_create(int64_t capacity, int max_batch, int H, int W, c
         require(c.min_depth > 0.f && c.min_depth < c.max_depth, "evaluator needs 0 < min_depth < max_depth");
         HIPCHK(hipSetDevice(device));
         auto e = std::make_unique<cad_evaluator>();
-        e->device = device; e->Bmax = max_batch; e->capacity = capacity; e->HW = (int64_t)H * W; e->W = W; e->cfg = c;
+        e->device = device; e->Bmax = max_batch; e->capacity = capacity; e->HW = (int64_t)H * W; e->W = W; e->H = H; e->cfg = c;
         e->nb = cad::eval_blocks(e->HW);
         const size_t tb = sizeof(double) * CAD_EVAL_METRICS * (size_t)capacity;
         const size_t pb = sizeof(double) * CAD_EVAL_METRICS * (size_t)max_batch * e->nb;
@@ -2187,6 +2197,7 @@ void cad_evaluator_destroy(cad_evaluator* e) {
     (void)hipFree(e->table);
     if (e->align_mem) (void)hipFree(e->align_mem);
     if (e->strata_table) (void)hipFree(e->strata_table);
+    if (e->geom_mem) (void)hipFree(e->geom_mem);
     delete e;
 }
 cad_status cad_evaluator_reset(cad_evaluator* e) {
@@ -2207,7 +2218,15 @@ cad_status cad_evaluator_update_k(cad_evaluator* e, const float* pred, const flo
         require(e->count + B <= e->capacity, "evaluator capacity exceeded");
         require(K || e->strata.n_angle_cuts == 0,
                 "the angle strata need the batch's K: use cad_evaluator_update_k (update with K)");
+        require(K || !e->geom, "the geometric metrics need the batch's K: use cad_evaluator_update_k (update with K)");
         HIPCHK(hipSetDevice(e->device));
+        // after the metrics pass, on the same stream: reads the alignment rows that pass scored
+        const auto geometry = [&] {
+            if (!e->geom) return;
+            cad::eval_geom_update(pred, gt, mask, K, B, e->H, e->W, e->cfg.min_depth, e->cfg.max_depth, e->cfg.clamp_pred,
+                                  e->align != CAD_ALIGN_NONE ? e->align_table : nullptr, e->count, e->geom_theta, e->geom_valid,
+                                  e->geom_part, e->geom_nb, e->geom_table, e->geom_ws, e->nb, e->geom_med, S(stream));
+        };
         if (strata_total_bins(e) > 0) {
             if (e->align != CAD_ALIGN_NONE)
                 cad::eval_align(e->align, pred, gt, mask, B, e->HW, e->cfg.min_depth, e->cfg.max_depth, e->align_ws, e->nb,
@@ -2216,6 +2235,7 @@ cad_status cad_evaluator_update_k(cad_evaluator* e, const float* pred, const flo
                                     e->part, e->nb, e->table, e->count, S(stream),
                                     e->align != CAD_ALIGN_NONE ? e->align_table : nullptr, e->strata, e->strata_part,
                                     e->strata_table);
+            geometry();
             HIPCHK(hipGetLastError());
             e->count += B;
             e->last = S(stream);
@@ -2226,6 +2246,7 @@ cad_status cad_evaluator_update_k(cad_evaluator* e, const float* pred, const flo
                             e->align_table, e->align_flags, e->count, S(stream));
         cad::eval_update(pred, gt, mask, B, e->HW, e->cfg.min_depth, e->cfg.max_depth, e->cfg.clamp_pred, e->part, e->nb,
                          e->table, e->count, S(stream), e->align != CAD_ALIGN_NONE ? e->align_table : nullptr);
+        geometry();
         HIPCHK(hipGetLastError());
         e->count += B;
         e->last = S(stream);
@@ -2399,6 +2420,145 @@ cad_status cad_eval_strata_finish(const double* sums, int64_t n, int bins, float
             eval_finish_row(pooled.data(), pm);   // the same sums as the present samples': absent rows are zero
             for (int k = 0; k < CAD_EVAL_METRICS; ++k) per_bin[b].pooled[k] = (float)pm[k];
         }
+    });
+}
+
+// ---------------- geometric evaluation ----------------
+cad_status cad_evaluator_set_geometry(cad_evaluator* e, int on) {
+    return guard([&] {
+        require(e != nullptr, "null evaluator");
+        require(e->count == 0, "geometry can only change while the evaluator is empty (count == 0)");
+        if (on && !e->geom_mem) {
+            require(e->HW < ((int64_t)1 << 31), "geometry needs H * W < 2^31");
+            HIPCHK(hipSetDevice(e->device));
+            const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+            const int gnb = cad::eval_geom_blocks(e->H, e->W);
+            const size_t cap = (size_t)e->capacity, px = (size_t)e->Bmax * (size_t)e->HW;
+            const size_t tb = up(sizeof(double) * CAD_GEOM_SUMS * cap);
+            const size_t pb = up(sizeof(double) * CAD_GEOM_SUMS * (size_t)e->Bmax * gnb);
+            const size_t mb = up(sizeof(float) * 2 * cap), thb = up(sizeof(float) * px), vb = up(px);
+            const size_t wb = cad::eval_align_ws_bytes(e->Bmax, e->nb);
+            void* mem = nullptr;
+            HIPCHK(hipMalloc(&mem, tb + pb + mb + thb + vb + wb));
+            // the select needs zero bins whichever stream the first update uses: wait for the fill here
+            hipError_t err = hipMemset(mem, 0, tb + pb + mb + thb + vb + wb);
+            if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+            if (err != hipSuccess) {
+                (void)hipFree(mem);
+                HIPCHK(err);
+            }
+            char* p = static_cast<char*>(mem);
+            e->geom_mem = mem;
+            e->geom_nb = gnb;
+            e->geom_table = reinterpret_cast<double*>(p);
+            e->geom_part = reinterpret_cast<double*>(p + tb);
+            e->geom_med = reinterpret_cast<float*>(p + tb + pb);
+            e->geom_theta = reinterpret_cast<float*>(p + tb + pb + mb);
+            e->geom_valid = reinterpret_cast<uint8_t*>(p + tb + pb + mb + thb);
+            e->geom_ws = cad::eval_align_ws_carve(p + tb + pb + mb + thb + vb, e->Bmax, e->nb);
+        }
+        e->geom = on ? 1 : 0;
+    });
+}
+int cad_evaluator_get_geometry(const cad_evaluator* e) { return e ? e->geom : 0; }
+cad_status cad_evaluator_geom_sums(cad_evaluator* e, double* out, void* stream) {
+    return guard([&] {
+        require(e && out, "null argument");
+        require(e->geom, "geometry is off (cad_evaluator_set_geometry)");
+        if (e->count == 0) return;
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipMemcpyAsync(out, e->geom_table, sizeof(double) * CAD_GEOM_SUMS * (size_t)e->count, hipMemcpyDeviceToHost,
+                              S(stream)));
+        HIPCHK(hipStreamSynchronize(S(stream)));
+    });
+}
+cad_status cad_evaluator_geom_medians(cad_evaluator* e, float* out, void* stream) {
+    return guard([&] {
+        require(e && out, "null argument");
+        require(e->geom, "geometry is off (cad_evaluator_set_geometry)");
+        if (e->count == 0) return;
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipMemcpy2DAsync(out, sizeof(float), e->geom_med, 2 * sizeof(float), sizeof(float), (size_t)e->count,
+                                hipMemcpyDeviceToHost, S(stream)));
+        HIPCHK(hipStreamSynchronize(S(stream)));
+    });
+}
+
+namespace {
+// one geometry row, its median and the valid count -> the nine metrics
+void geom_finish_row(const double* t, double med, double n, double* m) {
+    for (int k = 0; k < CAD_GEOM_METRICS; ++k) m[k] = 0.0;
+    const double nn = t[0];
+    if (nn > 0) {
+        m[0] = t[1] / nn;
+        m[1] = med;
+        m[2] = std::sqrt(t[2] / nn);
+        m[3] = t[3] / nn;
+        m[4] = t[4] / nn;
+        m[5] = t[5] / nn;
+        m[6] = nn;
+    }
+    if (n > 0) {
+        m[7] = t[6] / n;
+        m[8] = std::sqrt(t[7] / n);
+    }
+}
+}  // namespace
+
+cad_status cad_eval_geom_finish(const double* sums, const float* medians, const double* total_sums, int64_t n,
+                                float* per_sample, cad_geom_summary* s) {
+    return guard([&] {
+        require(n >= 0 && ((sums && medians && total_sums) || n == 0), "bad arguments");
+        std::vector<double> m((size_t)n * CAD_GEOM_METRICS);
+        for (int64_t i = 0; i < n; ++i)
+            geom_finish_row(sums + i * CAD_GEOM_SUMS, (double)medians[i], total_sums[i * CAD_EVAL_METRICS],
+                            m.data() + i * CAD_GEOM_METRICS);
+        if (per_sample)
+            for (size_t i = 0; i < m.size(); ++i) per_sample[i] = (float)m[i];
+        if (!s) return;
+        std::memset(s, 0, sizeof(*s));
+        s->count = n;
+        double pooled_sums[CAD_GEOM_SUMS] = {0}, pooled_n = 0.0, pooled[CAD_GEOM_METRICS];
+        for (int64_t i = 0; i < n; ++i) {
+            for (int k = 0; k < CAD_GEOM_SUMS; ++k) pooled_sums[k] += sums[i * CAD_GEOM_SUMS + k];
+            pooled_n += total_sums[i * CAD_EVAL_METRICS];
+            if (sums[i * CAD_GEOM_SUMS] > 0) ++s->count_normal;
+            if (total_sums[i * CAD_EVAL_METRICS] > 0) ++s->count_point;
+        }
+        geom_finish_row(pooled_sums, 0.0, pooled_n, pooled);
+        std::vector<double> col;
+        for (int k = 0; k < CAD_GEOM_METRICS; ++k) {
+            col.clear();
+            for (int64_t i = 0; i < n; ++i)
+                if ((k < 7 ? sums[i * CAD_GEOM_SUMS] : total_sums[i * CAD_EVAL_METRICS]) > 0)
+                    col.push_back(m[(size_t)i * CAD_GEOM_METRICS + k]);
+            s->pooled[k] = (float)pooled[k];
+            if (col.empty()) continue;
+            const size_t c = col.size();
+            double sum = 0.0, var = 0.0;
+            for (double v : col) sum += v;
+            const double mean = sum / c;
+            for (double v : col) var += (v - mean) * (v - mean);
+            std::sort(col.begin(), col.end());
+            s->mean[k] = (float)mean;
+            s->std[k] = (float)std::sqrt(var / c);
+            s->median[k] = (float)(c % 2 ? col[c / 2] : 0.5 * (col[c / 2 - 1] + col[c / 2]));
+            s->min[k] = (float)col.front();
+            s->max[k] = (float)col.back();
+        }
+        s->pooled[1] = std::numeric_limits<float>::quiet_NaN();   // a pooled median is not defined
+    });
+}
+
+cad_status cad_depth_normals(const float* depth, const float* K, const uint8_t* mask, int B, int H, int W, float min_depth,
+                             float max_depth, float* normals, uint8_t* valid, void* stream) {
+    return guard([&] {
+        require(depth && K && (normals || valid), "null argument");
+        require(B > 0 && H > 0 && W > 0, "depth_normals: B, H and W must be positive");
+        require((int64_t)H * W < ((int64_t)1 << 31), "depth_normals needs H * W < 2^31");
+        require(min_depth < max_depth, "depth_normals: min_depth must be below max_depth");
+        cad::depth_normals(depth, K, mask, B, H, W, min_depth, max_depth, normals, valid, nullptr, 0, 0, 0, nullptr, S(stream));
+        HIPCHK(hipGetLastError());
     });
 }
 

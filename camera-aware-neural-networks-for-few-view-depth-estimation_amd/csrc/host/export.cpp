@@ -227,6 +227,19 @@ cad_status cad_exporter_image(cad_exporter* e, const float* rgb, int B, const ca
     });
 }
 
+cad_status cad_exporter_normals(cad_exporter* e, const float* depth, const float* K, const uint8_t* mask, int B,
+                                const cad_render_opts* opts, uint8_t* rgb_out, void* stream) {
+    return xguard([&] {
+        need(e && depth && K && opts && rgb_out, "null argument");
+        need(B >= 1 && B <= e->Bmax, "batch exceeds the exporter's max_batch");
+        const Pane p = pane_of(e, opts);
+        XCHK(hipSetDevice(e->device));
+        cad::depth_normals(depth, K, mask, B, e->H, e->W, 0.f, __builtin_inff(), nullptr, nullptr, rgb_out, p.row_stride,
+                           p.col_off, p.image_stride, opts->invalid, S(stream));
+        XCHK(hipGetLastError());
+    });
+}
+
 cad_status cad_exporter_points(cad_exporter* e, const float* depth, const float* K, const float* rgb, const uint8_t* mask,
                                int B, int stride, float min_depth, float max_depth, void* records, int32_t* counts,
                                void* stream) {

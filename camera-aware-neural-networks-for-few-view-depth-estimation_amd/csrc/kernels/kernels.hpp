@@ -376,6 +376,26 @@ void eval_valid_medians(const float* pred, const float* gt, const uint8_t* mask,
                         float max_depth, const EvalAlignWs& ws, int nb, float* med, hipStream_t st);
 void eval_align(int mode, const float* pred, const float* gt, const uint8_t* mask, int B, int64_t HW, float min_depth,
                 float max_depth, const EvalAlignWs& ws, int nb, float* table, uint8_t* flags, int64_t base, hipStream_t st);
+// Geometric evaluation (eval_geom_kernels.hip): per sample the eight sums {n_normal, theta, theta^2,
+// #(theta < 11.25), #(theta < 22.5), #(theta < 30), e, e^2} of the surface-normal angular error theta (degrees)
+// and the 3-D point error e between the back-projected prediction and gt, into rows base .. base + B - 1 of
+// `table` ([rows][8] doubles), and the exact median of theta over the normal-valid pixels into med2
+// ([rows][2] floats, column 0; column 1 is the select's gt median).  theta / nvalid: [B][H*W] scratch, every
+// pixel written; part: [B][nb][8], nb = eval_geom_blocks(H, W); ws / nb_select: a zeroed select workspace
+// (eval_align_ws_*) for nb_select = eval_blocks(H*W) blocks; align: the evaluator's (scale, shift) table or
+// null.  H * W < 2^31.
+int eval_geom_blocks(int H, int W);
+void eval_geom_update(const float* pred, const float* gt, const uint8_t* mask, const float* K, int B, int H, int W,
+                      float min_depth, float max_depth, int clamp_pred, const float* align, int64_t base, float* theta,
+                      uint8_t* nvalid, double* part, int nb, double* table, const EvalAlignWs& ws, int nb_select, float* med2,
+                      hipStream_t st);
+// Normals of a depth map (B,1,H,W) from K (the closed form of eval_geom_kernels.hip); a pixel is valid when it
+// and its four neighbours are finite, lo < d < hi, mask != 0.  Nullable outputs: normals (B,3,H,W), zeros where
+// invalid; valid (B,H,W) bytes; rgb, an RGB8 HWC pane (strides in pixels) coloured rintf(255 ((n_x + 1) / 2,
+// (1 - n_y) / 2, (1 - n_z) / 2)), `invalid` where invalid.
+void depth_normals(const float* depth, const float* K, const uint8_t* mask, int B, int H, int W, float lo, float hi,
+                   float* normals, uint8_t* valid, uint8_t* rgb, int64_t row_stride, int64_t col_off, int64_t image_stride,
+                   const uint8_t invalid[3], hipStream_t st);
 void repack_conv_dgrad(const float* w, float* wd, int cout, int cin, hipStream_t st);
 void repack_convT_fwd(const float* wm, float* wf, int cin, int cout, hipStream_t st);
 // Per-step weight preparation in one launch (the weights change every step): a list of jobs, each

@@ -245,6 +245,28 @@ class Predictor:
         check(self.lib.cad_exporter_image(self.h, _p(r), r.shape[0], C.byref(o), _p(out), self._stream()), "cad_exporter_image")
         return out
 
+    def normals(self, depth, K, mask=None, invalid=(0, 0, 0), out=None, col_offset=0):
+        """(B,H,W,3) uint8 on the device: the surface normals of depth (B,1,H,W) from K (B,3,3), coloured
+        rint(255 * ((n_x + 1) / 2, (1 - n_y) / 2, (1 - n_z) / 2)), a frontal wall (128, 128, 255).  Pixels whose
+        own or neighbouring depth is invalid (not finite, <= 0, mask == 0), the border included, get `invalid`.
+        out / col_offset as in colorize."""
+        import torch
+        d, B = self._depth(depth)
+        Kc = self._f32(K, (3, 3), "K")
+        assert Kc.numel() == 9 * B, "K must be (B,3,3)"
+        m = self._mask(mask, d)
+        row = 0
+        if out is None:
+            out = torch.empty((B, self.height, self.width, 3), dtype=torch.uint8, device=self.device)
+        else:
+            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 4
+            assert out.shape[0] >= B and out.shape[1] == self.height and out.shape[3] == 3
+            row = out.shape[2]
+        o = self._opts(invalid=invalid, row_stride=row, col_offset=col_offset)
+        check(self.lib.cad_exporter_normals(self.h, _p(d), _p(Kc), _p(m), B, C.byref(o), _p(out), self._stream()),
+              "cad_exporter_normals")
+        return out
+
     def to_uint16(self, depth, units_per_metre: float = 1000.0):
         """(B,H,W) uint16 on the device: rint(depth * units_per_metre) clamped to 65535; 0 where the depth is
         not finite or not positive (1000: SUN RGB-D's millimetre PNGs)."""

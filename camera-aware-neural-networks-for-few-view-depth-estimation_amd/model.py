@@ -508,10 +508,13 @@ class Evaluator:
 
     depth_bins / angle_bins: ascending cuts in metres / in degrees off the optical axis (cad.h, "stratified
     evaluation"); update() then also keeps the twelve sums per sample and per stratum, strata(axis) returns
-    them.  With angle_bins, update() needs the batch's K."""
+    them.  With angle_bins, update() needs the batch's K.
+
+    geometry: also keep the surface-normal and 3-D point sums of every sample (cad.h, "geometric
+    evaluation"); update() then needs the batch's K and geometry() returns them."""
 
     def __init__(self, capacity, max_batch, H, W, min_depth=0.1, max_depth=10.0, clamp_pred=True, device=0,
-                 align="none", depth_bins=None, angle_bins=None):
+                 align="none", depth_bins=None, angle_bins=None, geometry=False):
         mode = _abi.eval_align_mode(align)
         strata = _abi.strata_config(depth_bins, angle_bins)
         self.min_depth, self.max_depth = float(min_depth), float(max_depth)
@@ -528,6 +531,29 @@ class Evaluator:
             check(self.lib.cad_evaluator_set_alignment(self.h, mode), "cad_evaluator_set_alignment")
         if strata.n_depth_cuts or strata.n_angle_cuts:
             self._set_strata(strata)
+        if geometry:
+            self.set_geometry(True)
+
+    def set_geometry(self, on=True):
+        """Turn the geometric metrics on or off; allowed only while count == 0 (CadError otherwise)."""
+        check(self.lib.cad_evaluator_set_geometry(self.h, int(bool(on))), "cad_evaluator_set_geometry")
+
+    @property
+    def geometry_on(self) -> bool:
+        return bool(self.lib.cad_evaluator_get_geometry(self.h))
+
+    def geometry(self) -> dict:
+        """{"sums" (count, 8) float64 {n_normal, theta, theta^2, #<11.25, #<22.5, #<30, e, e^2}, "medians"
+        (count,) float32 median theta, "metrics" (count, 9) float32 in GEOM_KEYS order, "summary"}.  CadError
+        while geometry is off."""
+        sums = np.zeros((self.count, _abi.GEOM_SUMS), np.float64)
+        med = np.zeros((self.count,), np.float32)
+        check(self.lib.cad_evaluator_geom_sums(self.h, sums.ctypes.data_as(C.POINTER(C.c_double)), _stream(self.device)),
+              "cad_evaluator_geom_sums")
+        check(self.lib.cad_evaluator_geom_medians(self.h, med.ctypes.data_as(_abi.FP), _stream(self.device)),
+              "cad_evaluator_geom_medians")
+        per, summary = eval_geom_finish(sums, med, self.sums())
+        return {"sums": sums, "medians": med, "metrics": per, "summary": summary}
 
     def _set_strata(self, cfg):
         check(self.lib.cad_evaluator_set_strata(self.h, C.byref(cfg)), "cad_evaluator_set_strata")
@@ -547,7 +573,7 @@ class Evaluator:
     def update(self, pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | None = None,
                K: torch.Tensor | None = None):
         """Append the B samples of pred / gt (B,1,H,W) [mask: (B,1,H,W), nonzero = valid; K: (B,3,3), the
-        batch's intrinsics, required with angle_bins]."""
+        batch's intrinsics, required with angle_bins or geometry]."""
         B = pred.shape[0]
         assert pred.numel() == gt.numel() == B * self.height * self.width, "pred / gt must be (B,1,H,W)"
         m = None
@@ -658,6 +684,55 @@ def eval_strata_finish(sums):
     return per, [_summary_dict(summ[b]) for b in range(bins)]
 
 
+GEOM_KEYS = _abi.GEOM_KEYS   # cad.h's CAD_GEOM_METRICS order
+
+
+def eval_geom_finish(sums, medians, total_sums):
+    """cad_eval_geom_finish (host only): (N, 8) geometry sums, (N,) medians and the samples' (N, 12) total rows
+    (column 0, the valid count, divides the point sums) -> ((N, 9) float32 metrics in GEOM_KEYS order, summary
+    dict {"count", "count_normal", "count_point", "mean" | ... | "pooled": {key: value}}).  The normal
+    statistics run over the samples with a normal-valid pixel, the point statistics over those with a valid
+    pixel; the pooled median is NaN."""
+    sums = np.ascontiguousarray(sums, np.float64)
+    medians = np.ascontiguousarray(medians, np.float32)
+    total = np.ascontiguousarray(total_sums, np.float64)
+    if sums.ndim != 2 or sums.shape[1] != _abi.GEOM_SUMS:
+        raise ValueError("sums must be (N, 8)")
+    n = sums.shape[0]
+    if medians.shape != (n,) or total.shape != (n, 12):
+        raise ValueError("medians must be (N,) and total_sums (N, 12)")
+    per = np.zeros((n, len(GEOM_KEYS)), np.float32)
+    s = _abi.GeomSummary()
+    DP = C.POINTER(C.c_double)
+    check(_abi.load().cad_eval_geom_finish(sums.ctypes.data_as(DP), medians.ctypes.data_as(_abi.FP), total.ctypes.data_as(DP),
+                                           n, per.ctypes.data_as(_abi.FP), C.byref(s)), "cad_eval_geom_finish")
+    out = {"count": int(s.count), "count_normal": int(s.count_normal), "count_point": int(s.count_point)}
+    for stat in ("mean", "std", "median", "min", "max", "pooled"):
+        out[stat] = {k: float(getattr(s, stat)[i]) for i, k in enumerate(GEOM_KEYS)}
+    return per, out
+
+
+def depth_normals(depth, K, mask=None, min_depth=0.1, max_depth=10.0):
+    """Surface normals of depth (B,1,H,W) from K (B,3,3) on the device (cad_depth_normals): (normals (B,3,H,W)
+    float32, zeros where invalid; valid (B,1,H,W) bool).  A pixel is valid when it and its four neighbours
+    are finite, strictly inside (min_depth, max_depth) [and mask != 0]; n faces the camera (n_z < 0)."""
+    lib = _abi.load()
+    B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
+    assert depth.numel() == B * H * W and depth.dtype == torch.float32, "depth must be (B,1,H,W) float32"
+    assert K.numel() == B * 9 and K.dtype == torch.float32, "K must be (B,3,3) float32"
+    d, Kc = depth.contiguous(), K.contiguous()
+    m = None
+    if mask is not None:
+        assert mask.numel() == depth.numel(), "mask must be (B,1,H,W)"
+        mt = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else mask.to(torch.uint8).contiguous()
+        m = C.c_void_p(mt.data_ptr())
+    normals = torch.empty((B, 3, H, W), dtype=torch.float32, device=depth.device)
+    valid = torch.empty((B, 1, H, W), dtype=torch.uint8, device=depth.device)
+    check(lib.cad_depth_normals(_ptr(d), _ptr(Kc), m, B, H, W, min_depth, max_depth, _ptr(normals), C.c_void_p(valid.data_ptr()),
+                                _stream(depth.device)), "cad_depth_normals")
+    return normals, valid.bool()
+
+
 def strata_angle_thresholds(angle_bins) -> np.ndarray:
     """The fp32 tan^2 thresholds the evaluator compares rho^2 with, for angle cuts in degrees (host only)."""
     cuts = np.ascontiguousarray(angle_bins, np.float32)
@@ -710,13 +785,14 @@ def _eval_forward(model, rgb, K):
 
 
 def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False, align="none",
-             depth_bins=None, angle_bins=None):
+             depth_bins=None, angle_bins=None, geometry=False):
     """ModelEvaluator: eval-mode forwards over `batches` of (rgb, gt, K[, mask]) device tensors, every
     prediction scored on device (Evaluator.update) with no host synchronisation inside the loop; the
     model's train / eval mode is restored.  Returns {"keys", "per_sample" (N,12), "summary",
     "forward_ms_per_image" (events around the whole loop), "parameters", "align", "alignment" (N,2)
     (scale, shift) per sample[, "predictions" (the raw ones)]}.  depth_bins / angle_bins (Evaluator): also
-    "strata": {"depth" | "angle": Evaluator.strata(axis)} for the axes asked for."""
+    "strata": {"depth" | "angle": Evaluator.strata(axis)} for the axes asked for.  geometry=True: also
+    "geometry": Evaluator.geometry(), the surface-normal and 3-D point metrics from each batch's K."""
     _abi.eval_align_mode(align)
     batches = list(batches)
     if not batches:
@@ -725,8 +801,9 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
     dev = batches[0][0].device
     n = sum(int(b[0].shape[0]) for b in batches)
     ev = Evaluator(n, max(int(b[0].shape[0]) for b in batches), H, W, min_depth, max_depth, clamp_pred,
-                   device=dev.index or 0, align=align, depth_bins=depth_bins, angle_bins=angle_bins)
-    with_k = ev.strata_bins("angle") > 0
+                   device=dev.index or 0, align=align, depth_bins=depth_bins, angle_bins=angle_bins,
+                   geometry=geometry)
+    with_k = ev.strata_bins("angle") > 0 or ev.geometry_on
     was_training = bool(getattr(model, "training", True))
     model.eval()
     preds = []
@@ -751,6 +828,8 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
     axes = [a for a in ("depth", "angle") if ev.strata_bins(a) > 0]
     if axes:
         out["strata"] = {a: ev.strata(a) for a in axes}
+    if ev.geometry_on:
+        out["geometry"] = ev.geometry()
     return out
 
 

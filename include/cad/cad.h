@@ -545,6 +545,68 @@ cad_status cad_strata_angle_thresholds(const float* cuts_deg, int n, float* out)
  * A bin no sample reaches: count 0 and zeros. */
 cad_status cad_eval_strata_finish(const double* sums, int64_t n, int bins, float* per_sample, cad_eval_summary* per_bin);
 
+/* ---- geometric evaluation: surface-normal and 3-D point metrics from K.  With geometry on, update_k also
+ * scores, per sample, quantities computed in camera space.  With fx = K[0], cx = K[2], fy = K[4], cy = K[5] of
+ * the sample's row-major K (the K of the H x W batch), u = column, v = row as fp32 values of the integer pixel
+ * index, x = (u - cx) / fx, y = (v - cy) / fy.  Per-pixel arithmetic is individually rounded fp32, accumulation
+ * is double in a fixed order, no floating-point atomics.
+ *   depths   ground truth g; prediction p = clamp(s pred + t), the value the metrics pass scores (the
+ *            sample's alignment, then the clamp_pred clamp); the valid set is the evaluator's.
+ *   normal   of a depth map d at (u, v), central differences of the back-projected points P = (x d, y d, d),
+ *            (P(u+1,v) - P(u-1,v)) x (P(u,v+1) - P(u,v-1)), in the cancellation-free closed form
+ *              a = d(u+1,v) - d(u-1,v)   A = (d(u+1,v) + d(u-1,v)) / fx
+ *              b = d(u,v+1) - d(u,v-1)   B = (d(u,v+1) + d(u,v-1)) / fy
+ *              c = (-a B, -A b, (A B + (x a) B) + (y A) b),   n = -c / |c|   (n_z < 0 for a frontal wall)
+ *   normal-valid  1 <= u <= W-2, 1 <= v <= H-2, the pixel and its four neighbours in the valid set, c_p and
+ *            c_g finite with |c| > 0.  No such pixel when H < 3 or W < 3.
+ *   theta    atan2f(|n_p x n_g|, n_p . n_g) * (float)(180 / pi), degrees in [0, 180]
+ *   e        |p - g| * sqrtf((1 + x x) + y y), the distance between the pixel's two back-projected points,
+ *            over the valid set (its count is the total row's n)
+ * Per sample a row of CAD_GEOM_SUMS doubles {n_normal, sum theta, sum theta^2, #(theta < 11.25f),
+ * #(theta < 22.5f), #(theta < 30.0f), sum e, sum e^2} and one fp32 median of theta over the normal-valid
+ * pixels, (theta_sorted[(n-1)/2] + theta_sorted[n/2]) * 0.5f, found exactly by CAD_ALIGN_MEDIAN's radix
+ * select (0 without a normal-valid pixel).  Metric order (CAD_GEOM_METRICS values per sample): normal_mean,
+ * normal_median, normal_rmse, normal_11.25, normal_22.5, normal_30, num_normal_pixels, point_mae, point_rmse.
+ * A sample's row and median are the same bits on every run, in whichever batch it arrives, from 16-byte
+ * aligned or unaligned tensors.  Per-stratum geometry is not kept: the strata rows are unaffected. */
+#define CAD_GEOM_SUMS 8
+#define CAD_GEOM_METRICS 9
+typedef struct {
+    int64_t count;         /* samples */
+    int64_t count_normal;  /* samples with n_normal > 0: the set of columns 0..6 */
+    int64_t count_point;   /* samples with a valid pixel: the set of columns 7, 8 */
+    float mean[CAD_GEOM_METRICS]; /* the strata's rule: over the samples of the column's set */
+    float std[CAD_GEOM_METRICS];
+    float median[CAD_GEOM_METRICS];
+    float min[CAD_GEOM_METRICS];
+    float max[CAD_GEOM_METRICS];
+    float pooled[CAD_GEOM_METRICS]; /* all samples' sums added, finished once; normal_median: NaN (not defined) */
+} cad_geom_summary;
+/* allowed only while count == 0.  on != 0 allocates the geometry table (capacity x 8 doubles), the medians,
+ * the theta and normal-valid maps (max_batch x H x W), the partials and a select workspace here, so that
+ * update still allocates nothing and never synchronises; needs H * W < 2^31.  While geometry is on
+ * cad_evaluator_update_k with a non-NULL K is the required form (cad_evaluator_update, or a NULL K:
+ * CAD_ERR_INVALID, table and count unchanged), and it issues the stencil pass, its finalise and the select's
+ * eight kernels after the metrics pass.  On an error nothing changes. */
+cad_status cad_evaluator_set_geometry(cad_evaluator* e, int on);
+int cad_evaluator_get_geometry(const cad_evaluator* e);
+/* host copies of the first count rows: count x 8 doubles / count floats; one synchronous copy on `stream`.
+ * CAD_ERR_INVALID while geometry is off. */
+cad_status cad_evaluator_geom_sums(cad_evaluator* e, double* out, void* stream);
+cad_status cad_evaluator_geom_medians(cad_evaluator* e, float* out, void* stream);
+/* host only (no device): n geometry rows, their n medians and the samples' total rows (n x 12 sums of
+ * cad_evaluator_sums; column 0, the valid count, is the n of the point statistics) -> per-sample metrics
+ * (n x 9, nullable; zeros for a sample outside a column's set) and the summary (nullable), in double, rounded
+ * to fp32 at the end.  A set no sample reaches: count 0 and zeros. */
+cad_status cad_eval_geom_finish(const double* sums, const float* medians, const double* total_sums, int64_t n,
+                                float* per_sample, cad_geom_summary* summary);
+/* stand-alone: normals of depth (B,1,H,W) device fp32 from K (B,3,3) by the closed form above.  A pixel is
+ * valid when it and its four neighbours are finite, min_depth < d < max_depth (strict) and mask != 0 (mask:
+ * B*H*W device bytes or NULL).  normals: (B,3,H,W) device fp32, zeros where invalid; valid: B*H*W device bytes;
+ * either may be NULL, not both.  One kernel on `stream`, no allocation, no synchronisation. */
+cad_status cad_depth_normals(const float* depth, const float* K, const uint8_t* mask, int B, int H, int W,
+                             float min_depth, float max_depth, float* normals, uint8_t* valid, void* stream);
+
 /* ---- conditioning: per-pixel unit ray directions (B,3,H,W) from K (B,3,3) ---- */
 cad_status cad_ray_directions(const float* K, int B, int H, int W, float* rays, void* stream);
 
@@ -931,6 +993,12 @@ cad_status cad_exporter_render(cad_exporter* e, const float* depth, const float*
 /* rgb (B,3,H,W) fp32 -> RGB8 HWC pane, rintf(clamp(c, 0, 1) * 255); opts' strides and offset as above */
 cad_status cad_exporter_image(cad_exporter* e, const float* rgb, int B, const cad_render_opts* opts, uint8_t* rgb_out,
                               void* stream);
+/* surface normals of depth (B,1,H,W) from K (B,3,3) (the closed form of "geometric evaluation") -> RGB8 HWC
+ * pane, (r, g, b) = rintf(255 ((n_x + 1) / 2, (1 - n_y) / 2, (1 - n_z) / 2)): a frontal wall is (128, 128, 255).
+ * A pixel is valid when it and its four neighbours are (cad_exporter_range's rule: finite, depth > 0,
+ * mask != 0); the others, the image border included, are opts->invalid.  opts' strides and offset as above. */
+cad_status cad_exporter_normals(cad_exporter* e, const float* depth, const float* K, const uint8_t* mask, int B,
+                                const cad_render_opts* opts, uint8_t* rgb_out, void* stream);
 /* point cloud: pixel (y, x) of image b is emitted iff y % stride == 0, x % stride == 0, isfinite(Z),
  * min_depth < Z < max_depth (strict) and mask != 0; its 16-byte record {float X, Y, Z; uint8 r, g, b, a} has
  * X = (x - cx) / fx * Z, Y = (y - cy) / fy * Z (fp32 subtract, divide, multiply), Z the depth's bits,

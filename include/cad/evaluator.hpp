@@ -84,6 +84,20 @@ inline cad_strata_config strataConfig(const std::vector<float>& depth_cuts, cons
     return c;
 }
 
+// Geometric evaluation (cad.h, "geometric evaluation"): the surface-normal and 3-D point metrics of a run
+inline const std::vector<const char*>& geometryKeys() {
+    static const std::vector<const char*> k = {"normal_mean", "normal_median", "normal_rmse", "normal_11.25", "normal_22.5",
+                                               "normal_30", "num_normal_pixels", "point_mae", "point_rmse"};
+    return k;
+}
+struct GeometryResult {
+    bool on = false;                 // false: geometry was off, everything below is empty
+    std::vector<double> sums;        // count x 8
+    std::vector<float> medians;      // count: median theta of each sample
+    std::vector<float> per_sample;   // count x 9 metrics, geometryKeys() order
+    cad_geom_summary summary{};      // the normal columns over the samples with a normal-valid pixel
+};
+
 // RAII handle of a cad_evaluator
 class MetricsTable {
 public:
@@ -114,6 +128,30 @@ public:
         cad::check(cad_evaluator_set_strata(h_, &c), "cad_evaluator_set_strata");
         depth_cuts_ = depth_cuts;
         angle_cuts_ = angle_cuts_deg;
+    }
+    // allowed only while count() == 0; allocates the geometry table, maps and workspace, so that update still
+    // allocates nothing.  While on, update needs the batch's K.
+    void setGeometry(bool on) { cad::check(cad_evaluator_set_geometry(h_, on ? 1 : 0), "cad_evaluator_set_geometry"); }
+    bool geometryOn() const { return cad_evaluator_get_geometry(h_) != 0; }
+    // the eight geometry sums per sample (count x 8); one synchronous copy on `stream`
+    std::vector<double> geometrySums(void* stream = nullptr) {
+        std::vector<double> s((size_t)count() * CAD_GEOM_SUMS);
+        cad::check(cad_evaluator_geom_sums(h_, s.data(), stream), "cad_evaluator_geom_sums");
+        return s;
+    }
+    // sums, medians, per-sample metrics and summary; synchronous copies on `stream` (on == false: geometry off)
+    GeometryResult geometry(void* stream = nullptr) {
+        GeometryResult r;
+        r.on = geometryOn();
+        if (!r.on) return r;
+        r.sums = geometrySums(stream);
+        r.medians.assign((size_t)count(), 0.f);
+        r.per_sample.assign((size_t)count() * CAD_GEOM_METRICS, 0.f);
+        cad::check(cad_evaluator_geom_medians(h_, r.medians.data(), stream), "cad_evaluator_geom_medians");
+        const std::vector<double> total = sums(stream);
+        cad::check(cad_eval_geom_finish(r.sums.data(), r.medians.data(), total.data(), count(), r.per_sample.data(), &r.summary),
+                   "cad_eval_geom_finish");
+        return r;
     }
     int strataBins(StrataAxis axis) const { return cad_evaluator_strata_bins(h_, (int)axis); }
     // one axis's sums, metrics and per-bin summaries; one synchronous copy on `stream` (bins == 0: axis off)
@@ -308,6 +346,7 @@ struct EvaluationConfig {
     // whether the result carries each sample's sensor
     std::vector<float> depth_cuts, angle_cuts_deg;
     bool by_sensor = false;
+    bool geometry = false;   // surface-normal and 3-D point metrics from each batch's K (cad.h, "geometric evaluation")
     // called after each batch's update with (index of its first sample, predictions (n,1,H,W), n).  A
     // callback that copies to the host synchronises; without one the loop never does.
     std::function<void(int64_t, const DeviceTensor&, int)> on_batch;
@@ -325,6 +364,7 @@ struct EvaluationResult {
     StrataResult depth_strata, angle_strata;   // bins == 0 unless EvaluationConfig asked for the axis
     std::vector<double> sums;                  // count x 12, filled with by_sensor or strata
     std::vector<std::string> sensors;          // one per sample, filled with by_sensor
+    GeometryResult geometry;                   // on == false unless EvaluationConfig asked for it
 };
 
 class ModelEvaluator {
@@ -380,6 +420,8 @@ public:
         MetricsTable table(ns, B, H, W, config_.min_depth, config_.max_depth, config_.clamp_pred, d, config_.align);
         const bool strata = !config_.depth_cuts.empty() || !config_.angle_cuts_deg.empty();
         if (strata) table.setStrata(config_.depth_cuts, config_.angle_cuts_deg);
+        if (config_.geometry) table.setGeometry(true);
+        const bool with_k = strata || config_.geometry;
         cad_loader* ring = L.ring(B, d, false);
         cad::check(cad_loader_start_epoch(ring, nullptr, ns), "evaluation");
         cad_event *t0 = nullptr, *t1 = nullptr;
@@ -396,7 +438,7 @@ public:
                 if (n == 0) break;   // the loader's end of epoch: the loop's only host-visible event
                 for (DeviceTensor* t : {&rgb_, &gt_, &K_, &pred_, &cam_}) t->shape[0] = n;
                 forward_(n);
-                if (strata) table.update(pred_, gt_, nullptr, K_);
+                if (with_k) table.update(pred_, gt_, nullptr, K_);
                 else table.update(pred_, gt_);
                 if (config_.on_batch) config_.on_batch(first, pred_, n);
                 first += n;
@@ -411,6 +453,7 @@ public:
                 r.angle_strata = table.strata(StrataAxis::Angle, 0.f, 90.f);
             }
             if (strata || config_.by_sensor) r.sums = table.sums();
+            if (config_.geometry) r.geometry = table.geometry();
             if (config_.by_sensor)
                 for (int64_t i = 0; i < table.count(); ++i) r.sensors.push_back(L.sensor(i));
             float ms = 0.f;

@@ -51,6 +51,12 @@ public:
         const cad_render_opts o = opts(pane);
         check(cad_exporter_image(h_, rgb, B, &o, pane.rgb, stream), "cad_exporter_image");
     }
+    // surface normals of depth from K (B,3,3) as colours: a frontal wall is (128, 128, 255); pixels without a
+    // valid five-point stencil, the border included, are black
+    void normals(const float* depth, const float* K, int B, const Pane& pane, void* stream = nullptr) {
+        const cad_render_opts o = opts(pane);
+        check(cad_exporter_normals(h_, depth, K, nullptr, B, &o, pane.rgb, stream), "cad_exporter_normals");
+    }
     // createComparisonViz's strip rgb | gt | pred | |pred - gt| of n samples into `panel` (device, n x H x 4W RGB8):
     // gt and pred in gt's range with `colormap`, the error pane in its own range with the hot table
     // (build/predict's <stem>_panel.png and the trainers' predictions/sample_<i> panels)
