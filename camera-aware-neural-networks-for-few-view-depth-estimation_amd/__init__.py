@@ -17,7 +17,7 @@ def __getattr__(name):
                 "Trainer", "Communicator", "save", "load", "clip_grad_norm_", "depth_metrics", "ray_directions", "camera_from_K",
                 "ResNetUNet", "GeometryAwareNetwork", "LightweightGeometryNetwork", "depth_metrics_full", "Evaluator",
                 "evaluate", "EVAL_KEYS", "valid_medians", "Optimizer", "eval_strata_finish", "strata_angle_thresholds",
-                "eval_geom_finish", "depth_normals", "GEOM_KEYS"):
+                "eval_geom_finish", "depth_normals", "GEOM_KEYS", "camera_view", "view", "resolve_view"):
         from . import model
         return getattr(model, name)
     if name == "lr_at":

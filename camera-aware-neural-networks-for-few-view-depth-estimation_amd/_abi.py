@@ -134,6 +134,61 @@ def strata_axis(axis) -> int:
     return STRATA_AXES[axis]
 
 
+class View(C.Structure):
+    """cad_view (cad.h, "virtual cameras"): a change of intrinsics and a rotation about the camera centre."""
+    _fields_ = [("zoom_x", F), ("zoom_y", F), ("shift_x", F), ("shift_y", F), ("yaw_deg", F), ("pitch_deg", F),
+                ("roll_deg", F)]
+
+    def __repr__(self):
+        return "View(" + ", ".join(f"{k}={getattr(self, k):g}" for k, _ in self._fields_) + ")"
+
+    def as_dict(self) -> dict:
+        return {k: float(getattr(self, k)) for k, _ in self._fields_}
+
+
+VIEW_AXES = ("zoom", "zoom_x", "zoom_y", "shift_x", "shift_y", "yaw", "pitch", "roll")   # build/evaluate --camera-sweep
+
+
+def view(zoom=None, zoom_x=1.0, zoom_y=1.0, shift_x=0.0, shift_y=0.0, yaw=0.0, pitch=0.0, roll=0.0) -> "View":
+    """A cad_view: zoom sets both zoom fields; angles in degrees.  What the library refuses (a non-finite field,
+    a non-positive zoom, an angle of magnitude >= 80 degrees) raises ValueError with its message; no device call."""
+    if zoom is not None:
+        zoom_x = zoom_y = zoom
+    v = View(*(float(x) for x in (zoom_x, zoom_y, shift_x, shift_y, yaw, pitch, roll)))
+    lib = load()
+    if lib.cad_view_check(C.byref(v)) != 0:
+        raise ValueError(lib.cad_last_error().decode(errors="replace"))
+    return v
+
+
+def view_label(axis, value) -> str:
+    """'zoom:1.5': the label build/evaluate gives the view of one --camera-sweep value (%.7g of the fp32 number)."""
+    return f"{axis}:{C.c_float(float(value)).value:.7g}"
+
+
+def sweep_views(camera_sweep) -> list:
+    """{"zoom": [0.7, 1.5], "yaw": [-7, 7]} -> [(label, View)], one view per value with every other field neutral,
+    in the mapping's order.  ValueError for an unknown axis, an empty list or a refused value; no device call."""
+    out = []
+    for axis, values in dict(camera_sweep).items():
+        if axis not in VIEW_AXES:
+            raise ValueError(f"camera_sweep axis must be one of {VIEW_AXES}, not {axis!r}")
+        values = [values] if isinstance(values, (int, float)) else list(values)
+        if not values:
+            raise ValueError(f"camera_sweep axis {axis!r}: no values")
+        for val in values:
+            out.append((view_label(axis, val), view(**{axis: val})))
+    return out
+
+
+def view_rotation(v: "View"):
+    """cad_view_rotation (host only): the view's R = Rz(roll) Rx(pitch) Ry(yaw), (3, 3) float32, P' = R P."""
+    import numpy as np
+    R = np.zeros((3, 3), np.float32)
+    check(load().cad_view_rotation(C.byref(v), R.ctypes.data_as(FP)), "cad_view_rotation")
+    return R
+
+
 COLORMAPS = {"gray": 0, "jet": 1, "hot": 2}   # CAD_CMAP_*; 3 = CAD_CMAP_CUSTOM (cad_exporter_set_lut)
 CMAP_CUSTOM = 3
 
@@ -295,6 +350,10 @@ SIGNATURES = {
     "cad_valid_medians": (I, [P, P, P, I, I, I, F, F, P, P]),
     "cad_eval_solve_alignment": (I, [I, C.POINTER(C.c_double), FP, FP]),
     "cad_ray_directions": (I, [P, I, I, I, P, P]),
+    "cad_view_check": (I, [C.POINTER(View)]),
+    "cad_view_rotation": (I, [C.POINTER(View), FP]),
+    "cad_view_resolve": (I, [C.POINTER(View), P, I, I, I, P, P, P]),
+    "cad_camera_view": (I, [P, P, P, P, P, P, I, I, I, P, P, P, P]),
     "cad_unet_debug_buffer": (I64, [P, C.c_char_p, FP, I64]),
     "cad_profile_enable": (I, [I]),
     "cad_profile_reset": (I, []),

@@ -6,8 +6,10 @@
 //                  [--split val|train] [--save-predictions] [--gpu 0] [--dry-run]
 //                  [--align none|median|log_mean|scale_shift]
 //                  [--depth-bins 1,2,3,5] [--angle-bins 10,20,30] [--by-sensor] [--geometry]
+//                  [--camera-sweep zoom:0.7,1.5]... [--view-intrinsics true|source]
 //   build/evaluate --compare A/per_sample.csv B/per_sample.csv [--metric abs_rel] [--seed 42]
 //   build/evaluate --compare A/per_sample_strata.csv B/per_sample_strata.csv --stratum depth:2 [--metric abs_rel]
+//   build/evaluate --compare A/per_sample_camera.csv B/per_sample_camera.csv --view zoom:1.5 [--metric abs_rel]
 //
 // The model (model.architecture, init_features, max_depth, variant, use_pcl, use_attention), the data
 // section and training.batch_size come from the training YAML, the keys build/train reads; the synthetic
@@ -30,6 +32,15 @@
 // geometry columns), per_sample_geometry.csv (index, the nine metrics; --compare reads it like per_sample.csv)
 // and a "Geometric metrics" report section: the surface-normal angular error and the 3-D point error of the
 // aligned, clamped prediction, from each sample's K.  The strata files are unaffected by it.
+// --camera-sweep AXIS:v1,v2,... (repeatable; axes zoom, zoom_x, zoom_y, shift_x, shift_y, yaw, pitch, roll; cad.h
+// "virtual cameras") scores the model under virtual cameras: each value is one view with every other field
+// neutral, applied on the device to every batch after its unchanged main pass, forwarded and scored into a table
+// of its own.  It adds camera_sweep.csv (one row per view: axis, value, num_samples, valid_share = the view's
+// valid pixels over the main pass's, then summary.csv's metric columns), per_sample_camera.csv (long form: axis,
+// value, index, the twelve metrics, scale, shift, aligned) and a "Camera Sweep" report section appended after
+// the report's closing rule; every other file keeps its bytes.  --view-intrinsics source gives the model the
+// sample's own K while the data is the warped one.  Strata and geometry are not computed per view.  --compare
+// with --view axis:value pairs the samples of that view in two per_sample_camera.csv files.
 // --compare with --stratum axis:bin pairs the samples present in that stratum in both long-form files.  Any
 // exception prints "Error: <what>" and exits 1, like build/train.
 #include <algorithm>
@@ -73,6 +84,9 @@ struct Args {
     bool save_predictions = false, dry_run = false, by_sensor = false, geometry = false;
     std::vector<float> depth_bins, angle_bins;   // cuts; empty: the option was not given
     std::string stratum;                         // --compare: "depth:2"
+    std::vector<NamedView> views;                // --camera-sweep, in command-line order
+    bool view_intrinsics_true = true;            // --view-intrinsics
+    std::string view;                            // --compare: "zoom:1.5"
 };
 
 void usage() {
@@ -92,8 +106,14 @@ void usage() {
                  "      --by-sensor       Metrics per manifest sensor_type\n"
                  "      --geometry        Surface-normal angular error and 3-D point error from each sample's K\n"
                  "                        (over the whole image: per-stratum geometry is not computed)\n"
+                 "      --camera-sweep arg  AXIS:v1,v2,...: score the model under virtual cameras, one per value; axes\n"
+                 "                        zoom, zoom_x, zoom_y, shift_x, shift_y (image widths / heights), yaw, pitch,\n"
+                 "                        roll (degrees).  May be repeated\n"
+                 "      --view-intrinsics arg  true: the model is given each view's K' (default); source: the\n"
+                 "                        sample's own K\n"
                  "      --compare A B     Paired comparison of two per_sample.csv files (no GPU use)\n"
                  "      --stratum arg     With --compare on two per_sample_strata.csv files: axis:bin, e.g. depth:2\n"
+                 "      --view arg        With --compare on two per_sample_camera.csv files: axis:value, e.g. zoom:1.5\n"
                  "      --metric arg      Column compared by --compare (default: abs_rel)\n"
                  "      --seed arg        Bootstrap seed of --compare (default: 42)\n"
                  "  -h, --help            Print help\n";
@@ -133,6 +153,43 @@ void check_cut_range(const std::string& opt, const std::vector<float>& cuts, flo
                                      ") " + unit);
 }
 
+// "zoom:0.7,1.5" -> one view per value, every other field neutral; refused values fail here, on the host
+const char* const kSweepAxes[] = {"zoom", "zoom_x", "zoom_y", "shift_x", "shift_y", "yaw", "pitch", "roll"};
+void parse_sweep(const std::string& opt, const std::string& spec, std::vector<NamedView>* views) {
+    const auto colon = spec.find(':');
+    const std::string axis = spec.substr(0, colon);
+    int ax = -1;
+    for (int i = 0; i < 8; ++i)
+        if (axis == kSweepAxes[i]) ax = i;
+    if (colon == std::string::npos || ax < 0)
+        throw std::runtime_error(opt + " '" + spec + "': expected AXIS:v1,v2,... with AXIS one of zoom, zoom_x, zoom_y, shift_x, "
+                                 "shift_y, yaw, pitch, roll" + (colon == std::string::npos ? "" : " (not '" + axis + "')"));
+    const std::string list = spec.substr(colon + 1);
+    std::string cell;
+    size_t count = 0;
+    for (std::stringstream ls(list); std::getline(ls, cell, ','); ++count) {
+        size_t used = 0;
+        float v = 0.f;
+        try {
+            v = std::stof(cell, &used);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+        if (cell.empty() || used != cell.size()) throw std::runtime_error(opt + " '" + spec + "': '" + cell + "' is not a number");
+        NamedView nv;
+        float* const field[8] = {nullptr,           &nv.view.zoom_x,  &nv.view.zoom_y,    &nv.view.shift_x,
+                                 &nv.view.shift_y,  &nv.view.yaw_deg, &nv.view.pitch_deg, &nv.view.roll_deg};
+        if (ax == 0) nv.view.zoom_x = nv.view.zoom_y = v;
+        else *field[ax] = v;
+        nv.label = axis + ":" + cut_str(v);
+        if (cad_view_check(&nv.view) != CAD_OK) throw std::runtime_error(opt + " '" + spec + "': " + cad_last_error());
+        for (const NamedView& o : *views)
+            if (o.label == nv.label) throw std::runtime_error(opt + " '" + spec + "': the view " + nv.label + " is given twice");
+        views->push_back(nv);
+    }
+    if (count == 0 || list.back() == ',') throw std::runtime_error(opt + " '" + spec + "': expected a list of values such as " + axis + ":0.7,1.5");
+}
+
 Args parse_args(int argc, char** argv) {
     Args a;
     for (int i = 1; i < argc; ++i) {
@@ -141,7 +198,7 @@ Args parse_args(int argc, char** argv) {
         const bool has_eq = k.rfind("--", 0) == 0 && eq != std::string::npos;
         if (has_eq) { v = k.substr(eq + 1); k = k.substr(0, eq); }
         auto next = [&]() -> std::string {
-            if (!v.empty() || (has_eq && (k == "--depth-bins" || k == "--angle-bins"))) return v;
+            if (!v.empty() || (has_eq && (k == "--depth-bins" || k == "--angle-bins" || k == "--camera-sweep"))) return v;
             if (i + 1 >= argc) throw std::runtime_error("missing value for " + k);
             return argv[++i];
         };
@@ -162,6 +219,12 @@ Args parse_args(int argc, char** argv) {
         else if (k == "--angle-bins") a.angle_bins = parse_cuts(k, next());
         else if (k == "--by-sensor") a.by_sensor = true;
         else if (k == "--geometry") a.geometry = true;
+        else if (k == "--camera-sweep") parse_sweep(k, next(), &a.views);
+        else if (k == "--view-intrinsics") {
+            const std::string m = next();
+            if (m != "true" && m != "source") throw std::runtime_error("--view-intrinsics '" + m + "': expected true or source");
+            a.view_intrinsics_true = m == "true";
+        } else if (k == "--view") a.view = next();
         else if (k == "--stratum") a.stratum = next();
         else if (k == "--metric") a.metric = next();
         else if (k == "--seed") a.seed = (uint32_t)std::stoul(next());
@@ -234,6 +297,64 @@ Column read_stratum_column(const std::string& path, const std::string& metric, c
     return c;
 }
 
+// the rows of one view of a per_sample_camera.csv (axis, value, index, metrics...)
+Column read_view_column(const std::string& path, const std::string& metric, const std::string& axis, float value) {
+    std::ifstream f(path);
+    if (!f) throw std::runtime_error("Cannot open " + path);
+    std::string line, cell;
+    if (!std::getline(f, line)) throw std::runtime_error(path + " is empty");
+    int col = -1, n = 0;
+    std::string names;
+    for (std::stringstream hs(line); std::getline(hs, cell, ','); ++n) {
+        static const char* head[3] = {"axis", "value", "index"};
+        if (n < 3 && cell != head[n])
+            throw std::runtime_error(path + ": the first columns must be axis,value,index (a per_sample_camera.csv file)");
+        if (n >= 3 && cell == metric) col = n;
+        if (n >= 3) names += (n > 3 ? ", " : "") + cell;
+    }
+    if (col < 3) throw std::runtime_error(path + " has no column '" + metric + "' (its columns: " + names + ")");
+    Column c;
+    while (std::getline(f, line)) {
+        if (line.empty()) continue;
+        std::vector<std::string> cells;
+        for (std::stringstream ls(line); std::getline(ls, cell, ',');) cells.push_back(cell);
+        if ((int)cells.size() <= col) throw std::runtime_error(path + ": short row '" + line + "'");
+        if (cells[0] != axis || std::stof(cells[1]) != value) continue;
+        c.index.push_back(std::stoll(cells[2]));
+        c.value.push_back(std::stod(cells[(size_t)col]));
+    }
+    return c;
+}
+
+int compare_view(const Args& a) {
+    const auto colon = a.view.find(':');
+    const std::string axis = a.view.substr(0, colon);
+    bool known = false;
+    for (const char* k : kSweepAxes) known = known || axis == k;
+    float value = 0.f;
+    size_t used = 0;
+    if (colon != std::string::npos) {
+        try {
+            value = std::stof(a.view.substr(colon + 1), &used);
+        } catch (const std::exception&) {
+            used = 0;
+        }
+    }
+    if (!known || colon == std::string::npos || used == 0 || used != a.view.size() - colon - 1)
+        throw std::runtime_error("--view '" + a.view + "': expected axis:value such as zoom:1.5");
+    const Column x = read_view_column(a.compare[0], a.metric, axis, value), y = read_view_column(a.compare[1], a.metric, axis, value);
+    for (const auto* c : {&x, &y})
+        if (c->index.empty())
+            throw std::runtime_error("the view " + a.view + " is not in " + (c == &x ? a.compare[0] : a.compare[1]));
+    if (x.index.size() != y.index.size())
+        throw std::runtime_error("the files hold " + std::to_string(x.index.size()) + " and " + std::to_string(y.index.size()) +
+                                 " samples of view " + a.view + ": a paired comparison needs the same samples");
+    if (x.index != y.index) throw std::runtime_error("the sample indices of view " + a.view + " do not match in the two files");
+    if (x.value.size() < 2) throw std::runtime_error("a paired comparison needs at least two samples in view " + a.view);
+    std::cout << eval_stats::compare_models(x.value, y.value, a.compare[0], a.compare[1], a.metric + " [" + a.view + "]", a.seed);
+    return 0;
+}
+
 int compare_stratum(const Args& a) {
     const auto colon = a.stratum.find(':');
     const std::string axis = a.stratum.substr(0, colon);
@@ -273,6 +394,8 @@ int compare_stratum(const Args& a) {
 }
 
 int compare(const Args& a) {
+    if (!a.stratum.empty() && !a.view.empty()) throw std::runtime_error("--stratum and --view cannot be combined");
+    if (!a.view.empty()) return compare_view(a);
     if (!a.stratum.empty()) return compare_stratum(a);
     const Column x = read_column(a.compare[0], a.metric), y = read_column(a.compare[1], a.metric);
     if (x.index.size() != y.index.size())
@@ -408,6 +531,67 @@ void write_geometry(const Args& a, const GeometryResult& g, std::ostream& rep, c
     rep << "  RMSE:      " << s.mean[8] << " ± " << s.std[8] << "\n\n";
 }
 
+// --camera-sweep: camera_sweep.csv, per_sample_camera.csv and the report section (after the report's closing rule)
+void write_camera_sweep(const Args& a, const EvaluationResult& r, std::ostream& rep, const std::string& bar, const std::string& rule) {
+    const auto& keys = metricKeys();
+    const auto split = [](const std::string& label) {
+        const auto colon = label.find(':');
+        return std::make_pair(label.substr(0, colon), label.substr(colon + 1));
+    };
+    {
+        std::ofstream f(a.output + "/camera_sweep.csv");
+        if (!f) throw std::runtime_error("cannot write " + a.output + "/camera_sweep.csv");
+        f << "axis,value,num_samples,valid_share";
+        for (const char* k : keys)
+            for (const char* s : {"mean", "std", "median", "pooled"}) f << "," << k << "_" << s;
+        f << "\n" << std::setprecision(9);
+        for (const ViewResult& v : r.views) {
+            const auto av = split(v.label);
+            f << av.first << "," << av.second << "," << v.per_sample.size() / CAD_EVAL_METRICS << "," << v.valid_share;
+            for (const char* k : keys)
+                for (const MetricMap* m : {&v.mean_metrics, &v.std_metrics, &v.median_metrics, &v.pooled_metrics}) f << "," << m->at(k);
+            f << "\n";
+        }
+    }
+    {
+        std::ofstream f(a.output + "/per_sample_camera.csv");
+        if (!f) throw std::runtime_error("cannot write " + a.output + "/per_sample_camera.csv");
+        f << "axis,value,index";
+        for (const char* k : keys) f << "," << k;
+        f << ",scale,shift,aligned\n" << std::setprecision(9);
+        for (const ViewResult& v : r.views) {
+            const auto av = split(v.label);
+            for (size_t i = 0; i < v.per_sample.size() / CAD_EVAL_METRICS; ++i) {
+                f << av.first << "," << av.second << "," << i;
+                for (int k = 0; k < CAD_EVAL_METRICS; ++k) f << "," << v.per_sample[i * CAD_EVAL_METRICS + (size_t)k];
+                f << "," << v.alignment[2 * i] << "," << v.alignment[2 * i + 1] << "," << (int)v.aligned[i] << "\n";
+            }
+        }
+    }
+    rep << rule << "\n                       Camera Sweep\n" << rule << "\n\n";
+    rep << "Virtual cameras, warped on the device; the model is given "
+        << (a.view_intrinsics_true ? "each view's K'" : "the sample's own K (--view-intrinsics source)") << ".\n";
+    rep << "Means over the samples; valid: the view's valid pixels over the unwarped run's.\n";
+    rep << std::fixed << std::setprecision(4);
+    std::vector<std::string> axes;
+    for (const ViewResult& v : r.views)
+        if (std::find(axes.begin(), axes.end(), split(v.label).first) == axes.end()) axes.push_back(split(v.label).first);
+    const auto row = [&](const std::string& name, float abs_rel, float rmse, float a1, double share) {
+        rep << "  " << std::left << std::setw(12) << name << std::right << std::setw(10) << abs_rel << std::setw(10) << rmse
+            << std::setw(10) << a1 << std::setw(9) << 100.0 * share << "%\n";
+    };
+    for (const std::string& axis : axes) {
+        rep << "\n  " << std::left << std::setw(12) << axis << std::right << std::setw(10) << "AbsRel" << std::setw(10) << "RMSE"
+            << std::setw(11) << "δ < 1.25" << std::setw(10) << "valid" << "\n";
+        row("(unwarped)", r.mean_metrics.at("abs_rel"), r.mean_metrics.at("rmse"), r.mean_metrics.at("delta_1.25"), 1.0);
+        for (const ViewResult& v : r.views)
+            if (split(v.label).first == axis)
+                row(split(v.label).second, v.mean_metrics.at("abs_rel"), v.mean_metrics.at("rmse"), v.mean_metrics.at("delta_1.25"),
+                    v.valid_share);
+    }
+    rep << "\n" << bar << "\n";
+}
+
 void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
     const auto& keys = metricKeys();
     const bool al = a.align != Alignment::None;
@@ -524,6 +708,7 @@ void write_outputs(const Args& a, const Config& c, const EvaluationResult& r) {
     }
     if (r.geometry.on) write_geometry(a, r.geometry, rep, rule);
     rep << bar << "\n";
+    if (!r.views.empty()) write_camera_sweep(a, r, rep, bar, rule);
 }
 
 int run(const Args& a) {
@@ -572,6 +757,11 @@ int run(const Args& a) {
         list("angle_bins", a.angle_bins);
         if (a.by_sensor) std::cout << ", \"by_sensor\": true";
         if (a.geometry) std::cout << ", \"geometry\": true";
+        if (!a.views.empty()) {
+            std::cout << ", \"camera_sweep\": [";
+            for (size_t j = 0; j < a.views.size(); ++j) std::cout << (j ? ", " : "") << "\"" << a.views[j].label << "\"";
+            std::cout << "], \"view_intrinsics\": \"" << (a.view_intrinsics_true ? "true" : "source") << "\"";
+        }
         std::cout << "}" << std::endl;
         return 0;
     }
@@ -600,6 +790,8 @@ int run(const Args& a) {
     ec.angle_cuts_deg = a.angle_bins;
     ec.by_sensor = a.by_sensor;
     ec.geometry = a.geometry;
+    ec.views = a.views;
+    ec.view_intrinsics_true = a.view_intrinsics_true;
     if (a.save_predictions)
         ec.on_batch = [&](int64_t first, const DeviceTensor& pred, int n) {
             const std::vector<float> h = pred.to_host();

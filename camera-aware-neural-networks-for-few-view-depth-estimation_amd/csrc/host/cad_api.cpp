@@ -2562,6 +2562,90 @@ cad_status cad_depth_normals(const float* depth, const float* K, const uint8_t* 
     });
 }
 
+// ---------------- virtual cameras ----------------
+extern "C++" {
+namespace {
+std::string view_num(float v) {
+    char buf[48];
+    std::snprintf(buf, sizeof buf, "%.9g", (double)v);
+    return buf;
+}
+void view_require(const cad_view* v) {
+    require(v != nullptr, "null view");
+    const std::pair<const char*, float> fields[] = {{"zoom_x", v->zoom_x},   {"zoom_y", v->zoom_y},       {"shift_x", v->shift_x},
+                                                    {"shift_y", v->shift_y}, {"yaw_deg", v->yaw_deg},     {"pitch_deg", v->pitch_deg},
+                                                    {"roll_deg", v->roll_deg}};
+    for (const auto& f : fields) require(std::isfinite(f.second), std::string("view: ") + f.first + " = " + view_num(f.second) + " is not finite");
+    for (int i = 0; i < 2; ++i)
+        require(fields[i].second > 0.f, std::string("view: ") + fields[i].first + " = " + view_num(fields[i].second) + " must be positive");
+    for (int i = 4; i < 7; ++i)
+        require(std::fabs(fields[i].second) < 80.f,
+                std::string("view: ") + fields[i].first + " = " + view_num(fields[i].second) + " must be inside (-80, 80) degrees");
+}
+// R = Rz(roll) Rx(pitch) Ry(yaw) in double, rounded to fp32 (+ 0.0: a zero entry is +0)
+void view_rotation(const cad_view& v, float* R9) {
+    const double rad = 3.14159265358979323846 / 180.0;
+    const double cy = std::cos(v.yaw_deg * rad), sy = std::sin(v.yaw_deg * rad);
+    const double cp = std::cos(v.pitch_deg * rad), sp = std::sin(v.pitch_deg * rad);
+    const double cr = std::cos(v.roll_deg * rad), sr = std::sin(v.roll_deg * rad);
+    const double Ry[9] = {cy, 0, -sy, 0, 1, 0, sy, 0, cy};
+    const double Rx[9] = {1, 0, 0, 0, cp, -sp, 0, sp, cp};
+    const double Rz[9] = {cr, -sr, 0, sr, cr, 0, 0, 0, 1};
+    double T[9], R[9];
+    const auto mul = [](const double* a, const double* b, double* c) {
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) c[i * 3 + j] = (a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j]) + a[i * 3 + 2] * b[6 + j];
+    };
+    mul(Rx, Ry, T);
+    mul(Rz, T, R);
+    for (int i = 0; i < 9; ++i) R9[i] = (float)(R[i] + 0.0);
+}
+}  // namespace
+}  // extern "C++"
+
+cad_status cad_view_check(const cad_view* view) {
+    return guard([&] { view_require(view); });
+}
+
+cad_status cad_view_rotation(const cad_view* view, float* R9) {
+    return guard([&] {
+        view_require(view);
+        require(R9 != nullptr, "null argument");
+        view_rotation(*view, R9);
+    });
+}
+
+cad_status cad_view_resolve(const cad_view* view, const float* K, int B, int H, int W, float* K_new, float* R, void* stream) {
+    return guard([&] {
+        view_require(view);
+        require(K && K_new && R, "null argument");
+        require(B > 0 && H > 0 && W > 0, "view_resolve: B = " + std::to_string(B) + ", H = " + std::to_string(H) + ", W = " +
+                                             std::to_string(W) + " must be positive");
+        cad::ViewParams p;
+        p.zoom_x = view->zoom_x;
+        p.zoom_y = view->zoom_y;
+        p.shift_x = view->shift_x;
+        p.shift_y = view->shift_y;
+        view_rotation(*view, p.R);
+        cad::view_resolve(p, K, B, H, W, K_new, R, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+
+cad_status cad_camera_view(const float* rgb, const float* depth, const uint8_t* mask, const float* K, const float* K_new,
+                           const float* R, int B, int H, int W, float* rgb_out, float* depth_out, uint8_t* valid_out,
+                           void* stream) {
+    return guard([&] {
+        require(rgb && depth && K && K_new && R && rgb_out && depth_out, "null argument");
+        require(B > 0 && H > 0 && W > 0, "camera_view: B = " + std::to_string(B) + ", H = " + std::to_string(H) + ", W = " +
+                                             std::to_string(W) + " must be positive");
+        require(B <= 65535, "camera_view needs B <= 65535");
+        require(H < (1 << 24) && W < (1 << 24) && (int64_t)H * W < ((int64_t)1 << 31), "camera_view needs H * W < 2^31");
+        cad::camera_view(rgb, depth, mask, K, K_new, R, B, H, W, rgb_out, depth_out, valid_out, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+
 // ---------------- scale-aligned evaluation ----------------
 cad_status cad_evaluator_set_alignment(cad_evaluator* e, int mode) {
     return guard([&] {

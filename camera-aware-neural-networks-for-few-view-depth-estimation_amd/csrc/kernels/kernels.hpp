@@ -476,6 +476,22 @@ struct BatchSample {
 void batch_assemble(const BatchSample* samples_dev, int B, int H, int W, bool any_aug, bool any_color, float* rgb,
                     float* depth, float* rgb_tmp, float* depth_tmp, hipStream_t st);
 
+// ---------------- virtual cameras (view_kernels.hip) ----------------
+// One view against a batch: zoom and shift as cad_view has them, R the view's rotation (row-major, P' = R P),
+// computed by the caller.
+struct ViewParams {
+    float zoom_x, zoom_y, shift_x, shift_y;
+    float R[9];
+};
+// K' (B,3,3) = K with fx' = zoom_x fx, fy' = zoom_y fy, cx' = cx + shift_x W, cy' = cy + shift_y H (fp32
+// products and sums), and R (B,3,3) = v.R for every sample.  One thread per sample.
+void view_resolve(const ViewParams& v, const float* K, int B, int H, int W, float* K_new, float* R, hipStream_t st);
+// The sample seen by the camera (K', R): rgb (B,3,H,W) bilinear with edge replicate, depth (B,1,H,W) nearest
+// and rescaled by 1 / d.z, valid (B,H,W bytes, nullable) — the rules at the top of view_kernels.hip.  mask:
+// B*H*W bytes or nullptr.  Outputs must not overlap the inputs or each other (CAD_NO_ALIAS).  B <= 65535.
+void camera_view(const float* rgb, const float* depth, const uint8_t* mask, const float* K, const float* K_new, const float* R,
+                 int B, int H, int W, float* rgb_out, float* depth_out, uint8_t* valid_out, hipStream_t st);
+
 // ---------------- conditioning (cond_kernels.hip, film_kernels.hip) ----------------
 void ray_directions(const float* K, int B, int H, int W, float* rays_nchw, hipStream_t st);
 void camera_from_K(const float* K, int B, float* cam4, hipStream_t st);            // a15

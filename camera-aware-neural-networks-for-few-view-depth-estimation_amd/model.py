@@ -784,16 +784,102 @@ def _eval_forward(model, rgb, K):
     return model.forward(rgb)
 
 
+view = _abi.view   # cad_view of keyword fields (zoom=, zoom_x=, shift_x=, yaw=, ...); ValueError for a refused value
+
+
+def _view_of(v):
+    if isinstance(v, _abi.View):
+        return v
+    if isinstance(v, dict):
+        return _abi.view(**v)
+    raise ValueError(f"view must be a cad.view(...) or a dict of its fields, not {type(v).__name__}")
+
+
+def _k33(K, B, what):
+    if not (isinstance(K, torch.Tensor) and K.is_cuda and K.dtype == torch.float32 and tuple(K.shape) == (B, 3, 3)):
+        raise ValueError(f"{what} must be a ({B},3,3) float32 device tensor")
+    return K.contiguous()
+
+
+def resolve_view(view, K: torch.Tensor, H: int, W: int):
+    """cad_view_resolve: one view against a batch's K (B,3,3) -> (K' (B,3,3), R (B,3,3)) on the device.
+    fx' = zoom_x fx, fy' = zoom_y fy, cx' = cx + shift_x W, cy' = cy + shift_y H; R = Rz(roll) Rx(pitch) Ry(yaw),
+    P' = R P, the same for every sample."""
+    v = _view_of(view)
+    if K.dim() != 3:
+        raise ValueError("K must be (B,3,3)")
+    Kc = _k33(K, K.shape[0], "K")
+    K_new, R = torch.empty_like(Kc), torch.empty_like(Kc)
+    check(_abi.load().cad_view_resolve(C.byref(v), _ptr(Kc), Kc.shape[0], int(H), int(W), _ptr(K_new), _ptr(R),
+                                       _stream(K.device)), "cad_view_resolve")
+    return K_new, R
+
+
+def camera_view(rgb, depth, K, view=None, K_new=None, R=None, mask=None, out=None):
+    """cad_camera_view: the batch as a virtual camera records it (cad.h, "virtual cameras").  rgb (B,3,H,W),
+    depth (B,1,H,W), K (B,3,3) float32 device tensors; either `view` (cad.view(...) or a dict of its fields, for
+    the whole batch) or per-sample K_new and / or R (B,3,3) (missing: K / the identity); mask (B,1,H,W), non-zero
+    = valid.  Returns (rgb', depth', K', valid (B,1,H,W) bool): rgb bilinear with edge replicate, depth nearest
+    and divided by d.z, 0 where nothing valid is seen.  out: (rgb', depth', valid uint8) tensors to write into;
+    they must not overlap the inputs."""
+    if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.float32 and rgb.dim() == 4 and rgb.shape[1] == 3):
+        raise ValueError("rgb must be a (B,3,H,W) float32 device tensor")
+    B, H, W = rgb.shape[0], rgb.shape[2], rgb.shape[3]
+    if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dtype == torch.float32 and tuple(depth.shape) == (B, 1, H, W)):
+        raise ValueError(f"depth must be a ({B},1,{H},{W}) float32 device tensor")
+    Kc = _k33(K, B, "K")
+    if view is not None:
+        if K_new is not None or R is not None:
+            raise ValueError("give either view or K_new / R, not both")
+        K_new, R = resolve_view(view, Kc, H, W)
+    else:
+        K_new = Kc if K_new is None else _k33(K_new, B, "K_new")
+        R = torch.eye(3, dtype=torch.float32, device=rgb.device).repeat(B, 1, 1) if R is None else _k33(R, B, "R")
+    m = None
+    if mask is not None:
+        if mask.numel() != B * H * W or not mask.is_cuda:
+            raise ValueError(f"mask must be a ({B},1,{H},{W}) device tensor")
+        mt = mask if mask.dtype == torch.uint8 and mask.is_contiguous() else mask.to(torch.uint8).contiguous()
+        m = C.c_void_p(mt.data_ptr())
+    if out is None:
+        rgb_o, depth_o = torch.empty_like(rgb, memory_format=torch.contiguous_format), torch.empty_like(depth, memory_format=torch.contiguous_format)
+        valid = torch.empty((B, 1, H, W), dtype=torch.uint8, device=rgb.device)
+    else:
+        rgb_o, depth_o, valid = out
+        if not (rgb_o.shape == rgb.shape and depth_o.shape == depth.shape and valid.numel() == B * H * W and
+                valid.dtype == torch.uint8 and valid.is_cuda and valid.is_contiguous()):
+            raise ValueError("out must be (rgb', depth', valid uint8) tensors of the input shapes")
+    check(_abi.load().cad_camera_view(_ptr(rgb.contiguous()), _ptr(depth.contiguous()), m, _ptr(Kc), _ptr(K_new), _ptr(R), B, H, W,
+                                      _ptr(rgb_o), _ptr(depth_o), C.c_void_p(valid.data_ptr()), _stream(rgb.device)),
+          "cad_camera_view")
+    return rgb_o, depth_o, K_new, valid.bool()
+
+
 def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False, align="none",
-             depth_bins=None, angle_bins=None, geometry=False):
+             depth_bins=None, angle_bins=None, geometry=False, camera_sweep=None, view_intrinsics="true"):
     """ModelEvaluator: eval-mode forwards over `batches` of (rgb, gt, K[, mask]) device tensors, every
     prediction scored on device (Evaluator.update) with no host synchronisation inside the loop; the
     model's train / eval mode is restored.  Returns {"keys", "per_sample" (N,12), "summary",
     "forward_ms_per_image" (events around the whole loop), "parameters", "align", "alignment" (N,2)
     (scale, shift) per sample[, "predictions" (the raw ones)]}.  depth_bins / angle_bins (Evaluator): also
     "strata": {"depth" | "angle": Evaluator.strata(axis)} for the axes asked for.  geometry=True: also
-    "geometry": Evaluator.geometry(), the surface-normal and 3-D point metrics from each batch's K."""
+    "geometry": Evaluator.geometry(), the surface-normal and 3-D point metrics from each batch's K.
+    camera_sweep ({"zoom": [0.7, 1.5], "yaw": [-7, 7]}: axis -> values, one view per value; or a list of (label,
+    cad.view(...))): after the main pass over a batch every view is applied to it on the device (camera_view),
+    forwarded and scored into a table of its own with the same range, clamp and align; "camera_sweep" is then a
+    list of {"label", "view", "per_sample" (N,12), "summary", "alignment", "aligned", "valid_share" (the view's
+    valid pixels over the main pass's)}.  view_intrinsics="true": the model is given each view's K';
+    "source": the sample's own K, while the data is still the warped one (how much does the model rely on
+    K?).  Strata and geometry are not computed per view; "forward_ms_per_image" stays the main pass's."""
     _abi.eval_align_mode(align)
+    if view_intrinsics not in ("true", "source"):
+        raise ValueError(f"view_intrinsics must be 'true' or 'source', not {view_intrinsics!r}")
+    if camera_sweep is None:
+        views = []
+    elif isinstance(camera_sweep, dict):
+        views = _abi.sweep_views(camera_sweep)
+    else:
+        views = [(str(label), _view_of(v)) for label, v in camera_sweep]
     batches = list(batches)
     if not batches:
         raise ValueError("evaluate: no batches")
@@ -804,25 +890,48 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
                    device=dev.index or 0, align=align, depth_bins=depth_bins, angle_bins=angle_bins,
                    geometry=geometry)
     with_k = ev.strata_bins("angle") > 0 or ev.geometry_on
+    max_b = max(int(b[0].shape[0]) for b in batches)
+    view_evs = [Evaluator(n, max_b, H, W, min_depth, max_depth, clamp_pred, device=dev.index or 0, align=align)
+                for _ in views]
     was_training = bool(getattr(model, "training", True))
     model.eval()
     preds = []
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    spans = []   # with views: one event pair per batch around the main pass alone
     try:
         t0.record()
         for b in batches:
             rgb, gt, K = b[0], b[1], b[2]
+            mask = b[3] if len(b) > 3 else None
+            if views:
+                spans.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                spans[-1][0].record()
             pred = _eval_forward(model, rgb, K)
-            ev.update(pred, gt, b[3] if len(b) > 3 else None, K if with_k else None)
+            ev.update(pred, gt, mask, K if with_k else None)
             if keep_predictions:
                 preds.append(pred.clone())
+            if views:
+                spans[-1][1].record()
+            for (_, v), vev in zip(views, view_evs):
+                rgb_v, gt_v, K_v, valid_v = camera_view(rgb, gt, K, view=v, mask=mask)
+                # (an identity view copies the depth, masked pixels included: its valid map carries the mask on)
+                vev.update(_eval_forward(model, rgb_v, K_v if view_intrinsics == "true" else K), gt_v,
+                           valid_v if mask is not None else None)
         t1.record()
         per = ev.metrics()   # the first host-visible event: one copy of the table
-        ms = t0.elapsed_time(t1)
+        ms = sum(a.elapsed_time(z) for a, z in spans) if views else t0.elapsed_time(t1)
     finally:
         model.train(was_training)
     out = {"keys": EVAL_KEYS, "per_sample": per, "summary": ev.summary(), "forward_ms_per_image": ms / n,
            "parameters": model.count_parameters(), "align": align, "alignment": ev.alignment()}
+    if views:
+        main_valid = float(ev.sums()[:, 0].sum())
+        out["view_intrinsics"] = view_intrinsics
+        out["camera_sweep"] = [
+            {"label": label, "view": v.as_dict(), "per_sample": vev.metrics(), "summary": vev.summary(),
+             "alignment": vev.alignment(), "aligned": vev.aligned(),
+             "valid_share": float(vev.sums()[:, 0].sum()) / main_valid if main_valid > 0 else 0.0}
+            for (label, v), vev in zip(views, view_evs)]
     if keep_predictions:
         out["predictions"] = torch.cat(preds)
     axes = [a for a in ("depth", "angle") if ev.strata_bins(a) > 0]

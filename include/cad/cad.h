@@ -610,6 +610,50 @@ cad_status cad_depth_normals(const float* depth, const float* K, const uint8_t* 
 /* ---- conditioning: per-pixel unit ray directions (B,3,H,W) from K (B,3,3) ---- */
 cad_status cad_ray_directions(const float* K, int B, int H, int W, float* rays, void* stream);
 
+/* ---- virtual cameras: the sample a camera with other intrinsics, or rotated about its centre, would have
+ * recorded.  Neither change has parallax, so the image follows from the recorded one by a homography and the
+ * ground-truth depth by the same homography and a per-pixel rescale of Z; no reference counterpart.
+ *
+ * Conventions: pixel centres at integer coordinates, depth is Z along the optical axis, x right, y down,
+ * z forward, skew ignored.  A view changes a sample's K (fx, fy, cx, cy) into K' and rotates the camera by R
+ * (row-major 3x3, P' = R P):
+ *   fx' = zoom_x fx, fy' = zoom_y fy, cx' = cx + shift_x W, cy' = cy + shift_y H     (fp32, on the device)
+ *   R = Rz(roll) Rx(pitch) Ry(yaw), Ry(t) = [[c,0,-s],[0,1,0],[s,0,c]] (a positive yaw turns the camera right:
+ *   the scene moves left), Rx(t) = [[1,0,0],[0,c,-s],[0,s,c]], Rz(t) = [[c,-s,0],[s,c,0],[0,0,1]]; computed
+ *   once on the host in double and rounded to fp32.
+ * Per output pixel (u', v'): d' = ((u' - cx') / fx', (v' - cy') / fy', 1), d = R^T d', source coordinate
+ * u = (fx d.x) / d.z + cx, v = (fy d.y) / d.z + cy.
+ *   rgb    bilinear between floor and floor + 1 of the coordinate clamped to [0, W-1] x [0, H-1] (edge
+ *          replicate); 0 where d.z <= 0 or the coordinate is not finite
+ *   depth  nearest (iu = floor(u + 0.5), iv = floor(v + 0.5)): Z' = Z(iv, iu) / d.z where the tap is inside
+ *          the image, d.z > 0, Z(iv, iu) is finite and positive and the source mask, if any, is non-zero
+ *          there; 0 otherwise (every loss and metric treats 0 as a hole)
+ *   valid  that predicate
+ * A sample whose R is the identity and whose K' equals K bit for bit is copied: rgb and depth keep their
+ * bits.  With R the identity alone d.z == 1 and Z' keeps the bits of the sampled Z.  The fp32 operations of
+ * the coordinates are individually rounded in the order written, so a fp32 restatement reproduces them. */
+typedef struct cad_view {
+    float zoom_x, zoom_y;                /* neutral: 1, 1 */
+    float shift_x, shift_y;              /* in image widths / heights; neutral: 0, 0 */
+    float yaw_deg, pitch_deg, roll_deg;  /* neutral: 0, 0, 0 */
+} cad_view;
+/* host only: CAD_ERR_INVALID, with a message naming the value, for a non-finite field, a non-positive zoom or
+ * an angle of magnitude >= 80 degrees */
+cad_status cad_view_check(const cad_view* view);
+/* host only: the view's R (9 floats, row-major) */
+cad_status cad_view_rotation(const cad_view* view, float* R9);
+/* view: host; K (B,3,3) device -> K_new (B,3,3) and R (B,3,3) device: every sample's K' and the view's R.
+ * Entries of K other than fx, fy, cx, cy are carried over.  One kernel on `stream`, one thread per sample.
+ * Refuses what cad_view_check refuses and B, H or W <= 0. */
+cad_status cad_view_resolve(const cad_view* view, const float* K, int B, int H, int W, float* K_new, float* R, void* stream);
+/* rgb (B,3,H,W), depth (B,1,H,W) device fp32, mask B*H*W device bytes or NULL, K, K_new, R (B,3,3) device fp32
+ * (per sample: a batch may mix views) -> rgb_out, depth_out, valid_out (B*H*W device bytes or NULL).  One
+ * kernel on `stream`, no allocation, no synchronisation.  Outputs must not overlap the inputs or each other
+ * (the alias check refuses that). */
+cad_status cad_camera_view(const float* rgb, const float* depth, const uint8_t* mask, const float* K, const float* K_new,
+                           const float* R, int B, int H, int W, float* rgb_out, float* depth_out, uint8_t* valid_out,
+                           void* stream);
+
 /* ---- batch assembly on device: decoded samples -> the step's (B,3,H,W) rgb, (B,1,H,W) depth,
  * (B,3,3) K.  Per sample: rgb = u8/255, depth = u16 * depth_scale, resized to H x W (rgb bilinear,
  * align_corners = false; depth nearest; K scaled), then — when aug is set — crop (window clamped to

@@ -334,6 +334,21 @@ inline void load_model_state(const std::string& path, Model& m) {
     if (!f || m.load(ts) != n) throw std::runtime_error("checkpoint does not match the model: " + path);
 }
 
+// Camera sweep (cad.h, "virtual cameras"): a labelled view, and what one view's pass over the loader gives
+struct NamedView {
+    std::string label;   // such as "zoom:1.5"
+    cad_view view{1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+};
+struct ViewResult {
+    std::string label;
+    cad_view view{};
+    std::vector<float> per_sample;   // count x 12, metricKeys() order
+    MetricMap mean_metrics, std_metrics, median_metrics, min_metrics, max_metrics, pooled_metrics;
+    std::vector<float> alignment;    // count x 2 (scale, shift)
+    std::vector<uint8_t> aligned;    // count
+    double valid_share = 0.0;        // the view's valid pixels over the main pass's
+};
+
 struct EvaluationConfig {
     float min_depth = 0.1f;
     float max_depth = 10.0f;
@@ -347,6 +362,11 @@ struct EvaluationConfig {
     std::vector<float> depth_cuts, angle_cuts_deg;
     bool by_sensor = false;
     bool geometry = false;   // surface-normal and 3-D point metrics from each batch's K (cad.h, "geometric evaluation")
+    // camera sweep: after the main pass over a batch each view is applied to it on the device, forwarded and
+    // scored into a table of its own (same range, clamp and align; no strata, no geometry).
+    // view_intrinsics_true == false: the model is given the sample's own K, the data is still the warped one.
+    std::vector<NamedView> views;
+    bool view_intrinsics_true = true;
     // called after each batch's update with (index of its first sample, predictions (n,1,H,W), n).  A
     // callback that copies to the host synchronises; without one the loop never does.
     std::function<void(int64_t, const DeviceTensor&, int)> on_batch;
@@ -365,6 +385,7 @@ struct EvaluationResult {
     std::vector<double> sums;                  // count x 12, filled with by_sensor or strata
     std::vector<std::string> sensors;          // one per sample, filled with by_sensor
     GeometryResult geometry;                   // on == false unless EvaluationConfig asked for it
+    std::vector<ViewResult> views;             // one per EvaluationConfig::views, in its order
 };
 
 class ModelEvaluator {
@@ -377,10 +398,10 @@ public:
         get_mode_ = [model] { return model->is_training(); };
         forward_ = [model, this](int n) {
             if (cad_unet_model(model->handle()) != CAD_MODEL_BASELINE) {
-                cad::check(cad_camera_from_K(K_.data, n, cam_.data, nullptr), "camera_from_K");
-                cad::check(cad_unet_forward_cam(model->handle(), rgb_.data, cam_.data, pred_.data, n, nullptr), "forward");
+                cad::check(cad_camera_from_K(in_K_->data, n, cam_.data, nullptr), "camera_from_K");
+                cad::check(cad_unet_forward_cam(model->handle(), in_rgb_->data, cam_.data, pred_.data, n, nullptr), "forward");
             } else {
-                cad::check(cad_unet_forward(model->handle(), rgb_.data, pred_.data, n, nullptr), "forward");
+                cad::check(cad_unet_forward(model->handle(), in_rgb_->data, pred_.data, n, nullptr), "forward");
             }
         };
     }
@@ -393,9 +414,9 @@ public:
         forward_ = [model, this](int n) {
             const int H = (int)rgb_.size(2), W = (int)rgb_.size(3);
             if (rays_.numel() == 0) rays_ = DeviceTensor::empty({config_.batch_size, 3, H, W}, config_.device);
-            cad::check(cad_ray_directions(K_.data, n, H, W, rays_.data, nullptr), "rays");
-            cad::check(cad_camera_from_K(K_.data, n, cam_.data, nullptr), "camera_from_K");
-            cad::check(cad_geonet_forward(model->handle(), rgb_.data, rays_.data, cam_.data, pred_.data, n, nullptr),
+            cad::check(cad_ray_directions(in_K_->data, n, H, W, rays_.data, nullptr), "rays");
+            cad::check(cad_camera_from_K(in_K_->data, n, cam_.data, nullptr), "camera_from_K");
+            cad::check(cad_geonet_forward(model->handle(), in_rgb_->data, rays_.data, cam_.data, pred_.data, n, nullptr),
                        "forward");
         };
     }
@@ -404,7 +425,10 @@ public:
     ModelEvaluator& operator=(const ModelEvaluator&) = delete;
 
     // Eval-mode forwards over the loader's samples in order, batch by batch, each batch scored on the
-    // device; the model's previous train / eval mode is restored.
+    // device; the model's previous train / eval mode is restored.  With EvaluationConfig::views each batch is
+    // still decoded once: after the unchanged main pass over it, every view is applied to it (cad_camera_view
+    // into the view buffers), forwarded and scored into that view's own table.  forward_ms_per_image then sums
+    // one event pair per batch around the main pass alone.
     EvaluationResult evaluate(SunRGBDLoader& L) {
         const bool restore_training = get_mode_();
         const int B = config_.batch_size, H = L.target_height(), W = L.target_width(), d = config_.device;
@@ -422,6 +446,28 @@ public:
         if (strata) table.setStrata(config_.depth_cuts, config_.angle_cuts_deg);
         if (config_.geometry) table.setGeometry(true);
         const bool with_k = strata || config_.geometry;
+        const size_t nv = config_.views.size();
+        for (const NamedView& v : config_.views) cad::check(cad_view_check(&v.view), ("view " + v.label).c_str());
+        std::vector<std::unique_ptr<MetricsTable>> vtables;
+        std::vector<std::pair<std::shared_ptr<cad_event>, std::shared_ptr<cad_event>>> spans;
+        if (nv) {
+            vrgb_ = DeviceTensor::empty({B, 3, H, W}, d);
+            vgt_ = DeviceTensor::empty({B, 1, H, W}, d);
+            vK_ = DeviceTensor::empty({B, 3, 3}, d);
+            vR_ = DeviceTensor::empty({B, 3, 3}, d);
+            for (size_t v = 0; v < nv; ++v)
+                vtables.push_back(std::make_unique<MetricsTable>(ns, B, H, W, config_.min_depth, config_.max_depth,
+                                                                 config_.clamp_pred, d, config_.align));
+            for (int64_t i = 0; i < (ns + B - 1) / B; ++i) {   // created up front: the loop allocates nothing
+                cad_event *a = nullptr, *z = nullptr;
+                cad::check(cad_event_create(&a), "event");
+                std::shared_ptr<cad_event> ga(a, cad_event_destroy);
+                cad::check(cad_event_create(&z), "event");
+                spans.emplace_back(ga, std::shared_ptr<cad_event>(z, cad_event_destroy));
+            }
+        }
+        in_rgb_ = &rgb_;
+        in_K_ = &K_;
         cad_loader* ring = L.ring(B, d, false);
         cad::check(cad_loader_start_epoch(ring, nullptr, ns), "evaluation");
         cad_event *t0 = nullptr, *t1 = nullptr;
@@ -432,18 +478,38 @@ public:
         EvaluationResult r;
         try {
             cad::check(cad_event_record(t0, nullptr), "event");
-            for (int64_t first = 0;;) {
+            size_t batch = 0;   // after the loop: the number of batches
+            for (int64_t first = 0;; ++batch) {
                 const int n = cad_loader_next(ring, rgb_.data, gt_.data, K_.data, nullptr);
                 if (n < 0) throw std::runtime_error(std::string("data loader: ") + cad_last_error());
                 if (n == 0) break;   // the loader's end of epoch: the loop's only host-visible event
                 for (DeviceTensor* t : {&rgb_, &gt_, &K_, &pred_, &cam_}) t->shape[0] = n;
+                if (nv) {
+                    if (batch >= spans.size()) throw std::runtime_error("ModelEvaluator: the loader gave more batches than planned");
+                    cad::check(cad_event_record(spans[batch].first.get(), nullptr), "event");
+                }
                 forward_(n);
                 if (with_k) table.update(pred_, gt_, nullptr, K_);
                 else table.update(pred_, gt_);
+                if (nv) cad::check(cad_event_record(spans[batch].second.get(), nullptr), "event");
                 if (config_.on_batch) config_.on_batch(first, pred_, n);
+                for (size_t v = 0; v < nv; ++v) {
+                    for (DeviceTensor* t : {&vrgb_, &vgt_, &vK_, &vR_}) t->shape[0] = n;
+                    cad::check(cad_view_resolve(&config_.views[v].view, K_.data, n, H, W, vK_.data, vR_.data, nullptr), "cad_view_resolve");
+                    cad::check(cad_camera_view(rgb_.data, gt_.data, nullptr, K_.data, vK_.data, vR_.data, n, H, W, vrgb_.data,
+                                               vgt_.data, nullptr, nullptr),
+                               "cad_camera_view");
+                    in_rgb_ = &vrgb_;
+                    in_K_ = config_.view_intrinsics_true ? &vK_ : &K_;
+                    forward_(n);
+                    in_rgb_ = &rgb_;
+                    in_K_ = &K_;
+                    vtables[v]->update(pred_, vgt_);
+                }
                 first += n;
             }
             cad::check(cad_event_record(t1, nullptr), "event");
+            const size_t batch_count = batch;
             cad_eval_summary s;
             r.per_sample = table.metrics(&s);
             r.align = config_.align;
@@ -457,7 +523,39 @@ public:
             if (config_.by_sensor)
                 for (int64_t i = 0; i < table.count(); ++i) r.sensors.push_back(L.sensor(i));
             float ms = 0.f;
-            cad::check(cad_event_elapsed_ms(t0, t1, &ms), "event");
+            if (nv) {
+                for (size_t i = 0; i < batch_count; ++i) {
+                    float part = 0.f;
+                    cad::check(cad_event_elapsed_ms(spans[i].first.get(), spans[i].second.get(), &part), "event");
+                    ms += part;
+                }
+            } else {
+                cad::check(cad_event_elapsed_ms(t0, t1, &ms), "event");
+            }
+            if (nv) {
+                double main_valid = 0.0;
+                const std::vector<double> ms_sums = table.sums();
+                for (size_t i = 0; i < ms_sums.size(); i += CAD_EVAL_METRICS) main_valid += ms_sums[i];
+                for (size_t v = 0; v < nv; ++v) {
+                    ViewResult vr;
+                    vr.label = config_.views[v].label;
+                    vr.view = config_.views[v].view;
+                    cad_eval_summary vs;
+                    vr.per_sample = vtables[v]->metrics(&vs);
+                    vr.alignment = vtables[v]->alignment(&vr.aligned);
+                    vr.mean_metrics = metricMap(vs.mean);
+                    vr.std_metrics = metricMap(vs.std);
+                    vr.median_metrics = metricMap(vs.median);
+                    vr.min_metrics = metricMap(vs.min);
+                    vr.max_metrics = metricMap(vs.max);
+                    vr.pooled_metrics = metricMap(vs.pooled);
+                    double valid = 0.0;
+                    const std::vector<double> vsums = vtables[v]->sums();
+                    for (size_t i = 0; i < vsums.size(); i += CAD_EVAL_METRICS) valid += vsums[i];
+                    vr.valid_share = main_valid > 0 ? valid / main_valid : 0.0;
+                    r.views.push_back(std::move(vr));
+                }
+            }
             r.forward_ms_per_image = (double)ms / (double)std::max<int64_t>(1, table.count());
             for (size_t i = 0; i < r.per_sample.size(); i += CAD_EVAL_METRICS)
                 r.sample_results.push_back(metricMap(r.per_sample.data() + i));
@@ -483,6 +581,8 @@ private:
     std::function<bool()> get_mode_;
     std::function<void(int)> forward_;
     DeviceTensor rgb_, gt_, K_, pred_, cam_, rays_;
+    DeviceTensor vrgb_, vgt_, vK_, vR_;                    // one view of the current batch
+    const DeviceTensor *in_rgb_ = &rgb_, *in_K_ = &K_;     // what forward_ reads: the batch, or a view of it
 };
 
 }  // namespace camera_aware_depth
