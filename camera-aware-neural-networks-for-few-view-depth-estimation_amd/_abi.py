@@ -373,6 +373,18 @@ SIGNATURES = {
     "cad_op_convT_dgrad": (I, [P, I64, I, I, P, I, P, I, I, I, P]),
     "cad_op_convT_wgrad": (I, [P, I, P, I64, I, I, P, I, I, I, P]),
     "cad_op_maxpool_fwd": (I, [P, I64, I, I, I, I, P, P, P]),
+    "cad_op_dense_fwd_bf16": (I, [P, I64, I, I, P, I64, I, I, P, I64, I, I, P, I64, P, P, P, I64, P]),
+    "cad_op_dense_wgrad_bf16": (I, [P, I64, I, I, P, I64, I, I, P, I64, I64, I64, P]),
+    "cad_op_im2col": (I, [P, I, I64, I, I, I, I, I, I, I, I, I, P, I, P]),
+    "cad_op_col2im": (I, [P, I, I, I, I, I, I, I, I, I, P, I64, P]),
+    "cad_op_maxpool3s2_fwd": (I, [P, I, I, I, I, P, P, P, P]),
+    "cad_op_maxpool3s2_bwd": (I, [P, P, I, I, I, I, P, P, I64, P]),
+    "cad_op_bn_add_relu": (I, [P, I, P, P, P, P, P, P, I64, I, I64, P, P, P, P, I64, P]),
+    "cad_op_relu_mask": (I, [P, I64, I, P, I, I64, P, P]),
+    "cad_op_mask_inplace": (I, [P, I64, I, P, I, I64, P]),
+    "cad_op_add_strided": (I, [P, I64, P, I64, I, I, I, I, I, I, P]),
+    "cad_op_copy_twin": (I, [P, I64, I, I, I, I, I, I, P, I64, I, P]),
+    "cad_op_transpose_split": (I, [P, I64, I, I, P, P]),
     "cad_batcher_create": (I, [I, I, I, I, C.POINTER(P)]),
     "cad_batcher_destroy": (None, [P]),
     "cad_batcher_assemble": (I, [P, C.c_void_p, I, P, P, P, P]),

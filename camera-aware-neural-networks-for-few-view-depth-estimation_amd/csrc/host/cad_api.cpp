@@ -3152,3 +3152,191 @@ cad_status cad_op_maxpool_fwd(const float* x, int64_t ldx, int C, int B, int H, 
 }
 
 }  // extern "C"
+
+// ---------------- config-5 operator entry points (resunet.cpp's launchers, one per call) ----------------
+namespace {
+// stream-ordered scratch of one entry point: freed on the stream when the call returns or throws
+struct OpScratch {
+    hipStream_t st;
+    std::vector<void*> held;
+    explicit OpScratch(hipStream_t s) : st(s) {}
+    template <class T>
+    T* take(size_t n) {
+        void* p = nullptr;
+        HIPCHK(hipMallocAsync(&p, sizeof(T) * std::max<size_t>(n, 4), st));
+        held.push_back(p);
+        return static_cast<T*>(p);
+    }
+    ~OpScratch() {
+        for (void* p : held) (void)hipFreeAsync(p, st);
+    }
+};
+bool conv_geom_ok(int B, int H, int W, int KH, int KW, int S, int P) {
+    return B > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && S > 0 && P >= 0 && H + 2 * P >= KH && W + 2 * P >= KW;
+}
+}  // namespace
+
+extern "C" {
+
+cad_status cad_op_dense_fwd_bf16(const void* x, int64_t ldx, int xcoff, int K, const void* w, int64_t ldw, int wcoff,
+                                 int N, void* y, int64_t ldy, int ycoff, int y_bf16, const float* add, int64_t ldadd,
+                                 const float* mask, float* mean, float* invstd, int64_t M, void* stream) {
+    return guard([&] {
+        require(cad::gemm_engine() == 2, "the dense GEMM on twins runs on the bf16 engine (CAD_GEMM_BF16)");
+        require(x && w && y && M > 0 && M <= INT32_MAX && N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 &&
+                    ldw % 8 == 0 && wcoff % 8 == 0 && xcoff >= 0 && wcoff >= 0 && ycoff >= 0,
+                "bad arguments (bf16 rows: ld, coff, K multiples of 8)");
+        require(ldx >= xcoff + K && ldw >= wcoff + K && ldy >= ycoff + N, "a view wider than its row");
+        require((mean != nullptr) == (invstd != nullptr), "mean and invstd come together");
+        const bool stats = mean != nullptr;
+        require(!stats || N % 4 == 0, "BN statistics: N % 4 == 0");
+        require(!mask || add, "a mask needs the added matrix");
+        require(ldadd >= 0 && !(add && ldadd && ldadd != ldy && (mask || ycoff || ldadd < N)),
+                "an added matrix of its own stride takes no mask / offset");
+        require(!(add && (stats || y_bf16)), "the added matrix needs fp32 output without statistics");
+        OpScratch scr(S(stream));
+        float* part = nullptr;
+        const int rows = cad::dense_stats_rows(M, N);
+        if (stats) part = scr.take<float>((size_t)rows * (2 * N + 1));
+        cad::dense_fwd_ps(cad::Split{x, ldx, xcoff}, K, cad::Split{w, ldw, wcoff}, N, static_cast<float*>(y), ldy, ycoff, M,
+                          part, S(stream), y_bf16 != 0, add, mask, ldadd);
+        if (stats) {
+            // gamma = 1, beta = 0; running statistics, scale and shift land in scratch
+            float* f = scr.take<float>((size_t)6 * N);
+            HIPCHK(hipMemsetAsync(f, 0, sizeof(float) * 6 * N, S(stream)));
+            const float one = 1.f;
+            int one_bits;
+            std::memcpy(&one_bits, &one, sizeof one_bits);
+            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f), one_bits, N, S(stream)));
+            double* dscr = scr.take<double>((size_t)(cad::colsum_slices(M) + 2) * 4 * N);
+            cad::bn_fwd_finalize(part, rows, N, M, f, f + N, f + 2 * N, f + 3 * N, 0.1f, 1e-5f, dscr, mean, invstd, f + 4 * N,
+                                 f + 5 * N, S(stream));
+        }
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_dense_wgrad_bf16(const void* dz, int64_t lddz, int dzcoff, int N, const void* x, int64_t ldx, int xcoff,
+                                   int K, float* dw, int64_t ldw, int64_t M, int64_t slab_max, void* stream) {
+    return guard([&] {
+        require(cad::gemm_engine() == 2, "the dense GEMM on twins runs on the bf16 engine (CAD_GEMM_BF16)");
+        require(dz && x && dw && M > 0 && M <= INT32_MAX && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0 && lddz % 8 == 0 &&
+                    dzcoff % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && dzcoff >= 0 && xcoff >= 0 && slab_max >= 0,
+                "bad arguments (bf16 rows: ld, coff, N, K multiples of 8)");
+        require(lddz >= dzcoff + N && ldx >= xcoff + K, "a view wider than its row");
+        require(ldw == K, "dense wgrad: dw rows must be dense (ldw == K)");
+        int64_t cap = std::max<int64_t>(cad::wgrad_slab_floats(N, K, (int)M), 1);
+        if (slab_max > 0) cap = std::min(cap, slab_max);
+        OpScratch scr(S(stream));
+        float* slab = scr.take<float>((size_t)cap);
+        cad::dense_wgrad_ps(cad::Split{dz, lddz, dzcoff}, N, cad::Split{x, ldx, xcoff}, K, dw, ldw, M, slab, cap, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_im2col(const void* x, int x_bf16, int64_t ldx, int xcoff, int C, int B, int H, int W, int KH, int KW,
+                         int stride, int pad, void* col, int Kp, void* stream) {
+    return guard([&] {
+        require(x && col && C > 0 && xcoff >= 0 && ldx >= xcoff + C && conv_geom_ok(B, H, W, KH, KW, stride, pad),
+                "bad arguments");
+        require(Kp % 8 == 0 && Kp >= KH * KW * C, "im2col: rows padded to Kp % 8 == 0, Kp >= KH KW C");
+        if (x_bf16) {
+            require(ldx % 8 == 0 && xcoff % 8 == 0, "im2col: bf16 rows need ldx, xcoff multiples of 8");
+            cad::im2col_ps(cad::Split{x, ldx, xcoff}, C, B, H, W, KH, KW, stride, pad, col, Kp, S(stream));
+        } else {
+            cad::im2col_f32(static_cast<const float*>(x), ldx, xcoff, C, B, H, W, KH, KW, stride, pad, col, Kp, S(stream));
+        }
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_col2im(const float* dcol, int Kc, int C, int B, int H, int W, int KH, int KW, int stride, int pad,
+                         float* dx, int64_t lddx, void* stream) {
+    return guard([&] {
+        require(dcol && dx && C > 0 && conv_geom_ok(B, H, W, KH, KW, stride, pad), "bad arguments");
+        require(C % 4 == 0 && Kc % 4 == 0 && lddx % 4 == 0 && Kc >= KH * KW * C && lddx >= C,
+                "col2im: C, Kc, lddx multiples of 4; Kc >= KH KW C; lddx >= C");
+        cad::col2im(dcol, Kc, C, B, H, W, KH, KW, stride, pad, dx, lddx, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_maxpool3s2_fwd(const float* x, int C, int B, int H, int W, float* out, uint8_t* idx, void* out_twin,
+                                 void* stream) {
+    return guard([&] {
+        require(x && idx && C > 0 && C % 4 == 0 && B > 0 && H > 0 && W > 0, "bad arguments (C % 4 == 0)");
+        cad::maxpool3s2_fwd(x, C, B, H, W, out, idx, out_twin, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_maxpool3s2_bwd(const float* dout, const uint8_t* idx, int C, int B, int H, int W, float* dx,
+                                 const float* add, int64_t ldadd, void* stream) {
+    return guard([&] {
+        require(dout && idx && dx && C > 0 && C % 4 == 0 && B > 0 && H > 0 && W > 0, "bad arguments (C % 4 == 0)");
+        require(!add || (ldadd >= C && ldadd % 4 == 0), "maxpool3s2_bwd: added matrix rows of ldadd >= C, ldadd % 4 == 0");
+        cad::maxpool3s2_bwd(dout, idx, C, B, H, W, dx, S(stream), add, ldadd);
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_bn_add_relu(const void* y, int y_bf16, const float* scale, const float* shift, const void* yd,
+                              const float* dscale, const float* dshift, const float* x, int64_t ldx, int C, int64_t M,
+                              float* out, void* out_twin, void* q, void* s, int64_t ldq, void* stream) {
+    return guard([&] {
+        require(y && scale && shift && out && C > 0 && C % 4 == 0 && M > 0, "bad arguments (C % 4 == 0)");
+        require(yd ? (dscale && dshift) : (x && ldx >= C && ldx % 4 == 0),
+                "bn_add_relu: a projection branch (yd, dscale, dshift) or an identity branch (x, ldx >= C, ldx % 4 == 0)");
+        require((q != nullptr) == (s != nullptr), "the MX-fp8 copy is q and s together");
+        cad::Mx8 qx;
+        if (q) {
+            require(C % 32 == 0 && ldq % 128 == 0 && ldq >= C, "bn_add_relu: the MX-fp8 copy needs C % 32 == 0, ldq % 128 == 0");
+            qx.q = q; qx.s = s; qx.ld = ldq; qx.coff = 0;
+        }
+        cad::bn_add_relu(static_cast<const float*>(y), scale, shift, static_cast<const float*>(yd), dscale, dshift, x, ldx, C,
+                         M, out, out_twin, S(stream), y_bf16 != 0, q ? &qx : nullptr);
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_relu_mask(const float* g, int64_t ldg, int gcoff, const float* out, int C, int64_t M, float* gs,
+                            void* stream) {
+    return guard([&] {
+        require(g && out && gs && C > 0 && C % 4 == 0 && ldg % 4 == 0 && gcoff % 4 == 0 && gcoff >= 0 && ldg >= gcoff + C &&
+                    M > 0,
+                "bad arguments (C, ldg, gcoff multiples of 4)");
+        cad::relu_mask(g, ldg, gcoff, out, C, M, gs, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_mask_inplace(float* y, int64_t ldy, int ycoff, const float* mask, int C, int64_t M, void* stream) {
+    return guard([&] {
+        require(y && mask && C > 0 && C % 4 == 0 && ldy % 4 == 0 && ycoff % 4 == 0 && ycoff >= 0 && ldy >= ycoff + C && M > 0,
+                "bad arguments (C, ldy, ycoff multiples of 4)");
+        cad::mask_inplace(y, ldy, ycoff, mask, C, M, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_add_strided(float* dst, int64_t lddst, const float* src, int64_t ldsrc, int scoff, int C, int B, int H,
+                              int W, int stride, void* stream) {
+    return guard([&] {
+        require(dst && src && C > 0 && C % 4 == 0 && lddst % 4 == 0 && ldsrc % 4 == 0 && scoff % 4 == 0 && scoff >= 0 &&
+                    lddst >= C && ldsrc >= scoff + C && B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2),
+                "bad arguments (C, lddst, ldsrc, scoff multiples of 4; stride 1 or 2)");
+        cad::add_strided(dst, lddst, src, ldsrc, scoff, C, B, H, W, stride, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_copy_twin(const void* src, int64_t lds, int scoff, int C, int B, int H, int W, int stride, void* dst,
+                            int64_t ldd, int dcoff, void* stream) {
+    return guard([&] {
+        require(src && dst && C > 0 && C % 8 == 0 && lds % 8 == 0 && scoff % 8 == 0 && ldd % 8 == 0 && dcoff % 8 == 0 &&
+                    scoff >= 0 && dcoff >= 0 && lds >= scoff + C && ldd >= dcoff + C && B > 0 && H > 0 && W > 0 &&
+                    (stride == 1 || stride == 2),
+                "bad arguments (bf16 rows: C, ld, coff multiples of 8; stride 1 or 2)");
+        cad::copy_twin(cad::Split{src, lds, scoff}, C, B, H, W, stride, dst, ldd, dcoff, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_transpose_split(const float* w, int64_t ldw, int N, int K, void* wt, void* stream) {
+    return guard([&] {
+        require(w && wt && N > 0 && K > 0 && ldw >= K, "bad arguments (ldw >= K)");
+        cad::transpose_split(w, ldw, N, K, wt, S(stream));
+        HIPCHK(hipGetLastError());
+    });
+}
+
+}  // extern "C"

@@ -843,6 +843,57 @@ cad_status cad_op_dense_x8(const void* xq, const void* xs, int64_t ldx, int K, c
 cad_status cad_op_conv3x3_x8(const void* xq, const void* xs, int64_t ldx, int cin, const void* wq, const void* ws,
                              int64_t ldw, int cout, float* y, int B, int H, int W, void* stream);
 
+/* ---- the config-5 network's operators, one launcher per call (tests, timing).  Rows are NHWC pixels;
+ * a twin is plain row-major bf16 (ld / coff in elements, multiples of 8).  The dense GEMMs require
+ * cad_set_gemm_engine(CAD_GEMM_BF16). */
+/* y[m][ycoff + n] = sum_k x[m][xcoff + k] w[n][wcoff + k] on bf16 twins (K % 8 == 0): fp32 rows of ldy, or
+ * bf16 rows with y_bf16.  add (nullable, fp32): y = x w^T + add, rows as y's when ldadd == 0 (add == y:
+ * in place) or dense rows of their own stride ldadd >= N (then no mask and ycoff == 0); mask (nullable,
+ * fp32, rows as y's, needs add): then y = 0 where mask is not > 0.  add takes fp32 y and no statistics.
+ * mean / invstd (nullable, together, N floats; N % 4 == 0): the BatchNorm batch statistics (eps 1e-5) of
+ * the stored y, from the GEMM epilogue's per-tile partials. */
+cad_status cad_op_dense_fwd_bf16(const void* x, int64_t ldx, int xcoff, int K, const void* w, int64_t ldw, int wcoff,
+                                 int N, void* y, int64_t ldy, int ycoff, int y_bf16, const float* add, int64_t ldadd,
+                                 const float* mask, float* mean, float* invstd, int64_t M, void* stream);
+/* dw[n][k] (fp32, ldw == K) = sum_m dz[m][dzcoff + n] x[m][xcoff + k] on bf16 twins; slab_max > 0 caps the
+ * split-K slab (floats), 0: the launcher's own size */
+cad_status cad_op_dense_wgrad_bf16(const void* dz, int64_t lddz, int dzcoff, int N, const void* x, int64_t ldx, int xcoff,
+                                   int K, float* dw, int64_t ldw, int64_t M, int64_t slab_max, void* stream);
+/* col[pix_out][k] (bf16 rows of Kp % 8 == 0) = x[pix_in][xcoff + c], k = (ky KW + kx) C + c; zero outside the
+ * image and for k >= KH KW C.  x: fp32 rows, or bf16 rows with x_bf16. */
+cad_status cad_op_im2col(const void* x, int x_bf16, int64_t ldx, int xcoff, int C, int B, int H, int W, int KH, int KW,
+                         int stride, int pad, void* col, int Kp, void* stream);
+/* dx[pix_in][c] (fp32 rows of lddx, overwritten) = sum over the taps reading pix_in of dcol[pix_out][tap C + c]
+ * (fp32 rows of Kc >= KH KW C); C % 4 == 0 */
+cad_status cad_op_col2im(const float* dcol, int Kc, int C, int B, int H, int W, int KH, int KW, int stride, int pad,
+                         float* dx, int64_t lddx, void* stream);
+/* MaxPool2d(3, 2, 1) on dense fp32 rows of C % 4 == 0: out (nullable) and its bf16 twin (nullable), idx =
+ * ky 3 + kx of the first maximum in scan order (NaN propagates); the backward gathers dout through idx
+ * into dx (overwritten), plus add rows of ldadd (nullable) */
+cad_status cad_op_maxpool3s2_fwd(const float* x, int C, int B, int H, int W, float* out, uint8_t* idx, void* out_twin,
+                                 void* stream);
+cad_status cad_op_maxpool3s2_bwd(const float* dout, const uint8_t* idx, int C, int B, int H, int W, float* dx,
+                                 const float* add, int64_t ldadd, void* stream);
+/* out[m][c] = relu(y scale + shift + r), r = yd dscale + dshift (projection: yd != NULL) or x rows of ldx
+ * (identity); y / yd dense fp32 rows, or bf16 with y_bf16; out dense fp32 [M][C], out_twin (nullable) its bf16
+ * twin, q / s (nullable, together; C % 32 == 0, ldq % 128 == 0) the twin's MX-fp8 copy */
+cad_status cad_op_bn_add_relu(const void* y, int y_bf16, const float* scale, const float* shift, const void* yd,
+                              const float* dscale, const float* dshift, const float* x, int64_t ldx, int C, int64_t M,
+                              float* out, void* out_twin, void* q, void* s, int64_t ldq, void* stream);
+/* gs[m][c] (dense) = g[m][gcoff + c] where out[m][c] > 0, else 0 (gs == g allowed for dense g) */
+cad_status cad_op_relu_mask(const float* g, int64_t ldg, int gcoff, const float* out, int C, int64_t M, float* gs,
+                            void* stream);
+/* y[m][ycoff + c] = 0 where mask[m][ycoff + c] (same rows) is not > 0 */
+cad_status cad_op_mask_inplace(float* y, int64_t ldy, int ycoff, const float* mask, int C, int64_t M, void* stream);
+/* dst[(b, s oy, s ox)][c] += src[(b, oy, ox)][scoff + c] over the ((H-1)/s + 1) x ((W-1)/s + 1) grid; s = 1, 2 */
+cad_status cad_op_add_strided(float* dst, int64_t lddst, const float* src, int64_t ldsrc, int scoff, int C, int B, int H,
+                              int W, int stride, void* stream);
+/* bf16 rows dst[(b, oy, ox)][dcoff + c] = src[(b, s oy, s ox)][scoff + c]; C % 8 == 0 */
+cad_status cad_op_copy_twin(const void* src, int64_t lds, int scoff, int C, int B, int H, int W, int stride, void* dst,
+                            int64_t ldd, int dcoff, void* stream);
+/* wt[k][n] (bf16, dense rows of N) = w[n][k] (fp32 rows of ldw), round-to-nearest-even */
+cad_status cad_op_transpose_split(const float* w, int64_t ldw, int N, int K, void* wt, void* stream);
+
 /* ---- config-5 network (BASELINE configs[4]): ResNet-50 encoder + U-Net decoder, bf16 operands ----
  * No reference counterpart: architecture in resunet.cpp / DESIGN.md §9;
  * torchvision ResNet-50 parameter names under "encoder.", decoder "dec4".."dec0", "out_conv".
