@@ -2001,7 +2001,10 @@ cad_status cad_lr_at(const cad_lr_opts* o, int epoch0, int num_epochs, float* lr
 cad_status cad_loss_create(float si, float gr, float sm, float rp, int max_batch, int height, int width, int device,
                            cad_loss** out) {
     return guard([&] {
-        require(out && max_batch >= 1 && height >= 2 && width >= 2, "bad loss arguments");
+        require(out && max_batch >= 1, "bad loss arguments");
+        // below 16 the k = 8 scale of the gradient-matching term has no x or y difference: the loss is 0/0
+        require(height >= 16, "loss: height " + std::to_string(height) + " is below 16 (the 4-scale gradient-matching pyramid)");
+        require(width >= 16, "loss: width " + std::to_string(width) + " is below 16 (the 4-scale gradient-matching pyramid)");
         HIPCHK(hipSetDevice(device));
         auto l = std::make_unique<cad_loss>();
         l->device = device; l->Bmax = max_batch; l->H = height; l->W = width;

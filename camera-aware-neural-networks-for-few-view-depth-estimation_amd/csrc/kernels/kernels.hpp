@@ -430,8 +430,9 @@ struct LossWorkspace {
     double* part;        // partial sums
     float* scal;         // scalars: see loss_kernels.hip
     float* pyr;          // log-pooled pyramid (pred, gt) for scales 1..3
-    int64_t part_cap;
+    int64_t part_cap;    // doubles in part: loss_fwd_bwd throws when a batch's layout exceeds it
 };
+// workspace sizes of a handle created for batches 1..B (both cover every smaller batch)
 int64_t loss_workspace_floats(int B, int H, int W);
 int64_t loss_part_doubles(int B, int H, int W);
 // total/components -> out[5] = {total, si, grad, smooth, reproj}; dpred = dL/dpred.  mask (nullable,

@@ -497,15 +497,23 @@ Geo make_geo(int B, int H, int W) {
 int nb_per_sample(int B, int H, int W) {
     return std::max(cdiv(cdiv(W, 64), kTPB / 64), std::min(cdiv(2048, B), cdiv((int64_t)H * W, kTPB)));
 }
+// doubles loss_fwd_bwd lays out for a batch of exactly B: the scalars and per-sample tails, then partA, partB
+int64_t part_layout_doubles(int B, int H, int W) {
+    return S_PB + 2 * B + 16 + (int64_t)B * nb_per_sample(B, H, W) * (kPA + kPB);
+}
 }  // namespace
 
 int64_t loss_workspace_floats(int B, int H, int W) {
-    // pyramid (avgP, logP, logG, gP for scales 1..3), then scale-0 logs and edge weights (lp, lg, wx, wy)
+    // pyramid (avgP, logP, logG, gP for scales 1..3), then scale-0 logs and edge weights (lp, lg, wx, wy);
+    // grows with B, so the size for max_batch covers every smaller batch
     return 4 * make_geo(B, H, W).pyr_n + 4 * (int64_t)B * H * W + 64;
 }
+// capacity for every batch 1..B of a handle created for B: B * ceil(2048 / B) is not monotone in B
+// (15 * 137 > 16 * 128), so a partial batch can need more partials than the full one
 int64_t loss_part_doubles(int B, int H, int W) {
-    const int nb = nb_per_sample(B, H, W);
-    return (int64_t)B * nb * (kPA + kPB) + S_PB + 2 * B + 64;
+    int64_t need = 0;
+    for (int b = 1; b <= B; ++b) need = std::max(need, part_layout_doubles(b, H, W));
+    return need + 48;
 }
 
 void loss_fwd_bwd(const float* pred, const float* gt, const float* rgb, const float* K, const uint8_t* mask, int B,
@@ -515,6 +523,10 @@ void loss_fwd_bwd(const float* pred, const float* gt, const float* rgb, const fl
     Geo g = make_geo(B, H, W);
     const int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
     const int nb = nb_per_sample(B, H, W);
+    if (part_layout_doubles(B, H, W) > ws.part_cap)
+        throw std::runtime_error("loss: batch " + std::to_string(B) + " lays out " +
+                                 std::to_string(part_layout_doubles(B, H, W)) + " partial-sum doubles, the workspace holds " +
+                                 std::to_string(ws.part_cap));
     double* dsc = ws.part;
     double* partA = dsc + S_PB + 2 * B + 16;
     double* partB = partA + (int64_t)B * nb * kPA;

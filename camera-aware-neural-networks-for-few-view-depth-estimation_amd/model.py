@@ -407,7 +407,8 @@ class CombinedDepthLoss:
     """CombinedDepthLoss(si_weight, grad_weight, smooth_weight, reproj_weight) with its backward
     (depth_loss.h:366-479).  forward_with_intrinsics / forward take the reference's optional
     valid_mask (bool or uint8 device tensor (B,1,H,W)); it replaces gt > 1e-6 in the SI and
-    reprojection terms, the gradient-matching term ignores it (depth_loss.h:137)."""
+    reprojection terms, the gradient-matching term ignores it (depth_loss.h:137).  height and width must be
+    at least 16 (the 4-scale gradient-matching pyramid; CadError otherwise); any batch 1..batch may be passed."""
 
     def __init__(self, si_weight=1.0, grad_weight=0.1, smooth_weight=0.001, reproj_weight=0.01, *, batch, height,
                  width, device=0):

@@ -390,7 +390,10 @@ int cad_plan_grad_buckets(const int64_t* stage_off, const int64_t* stage_cnt, in
 cad_status cad_model_grad_layout(int model, int in_channels, int init_features, int* nstages, int64_t stage_off[16],
                                  int64_t stage_cnt[16], int64_t* n_flat);
 
-/* ---- loss: CombinedDepthLoss ---- */
+/* ---- loss: CombinedDepthLoss ----
+ * height and width must be at least 16 (CAD_ERR_INVALID otherwise, the message names the value): below
+ * that the coarsest gradient-matching scale (avg_pool2d k = 8) has no horizontal or vertical difference
+ * and the loss is 0/0.  One handle serves every batch 1..max_batch. */
 cad_status cad_loss_create(float si_weight, float grad_weight, float smooth_weight, float reproj_weight,
                            int max_batch, int height, int width, int device, cad_loss** out);
 void cad_loss_destroy(cad_loss* l);
