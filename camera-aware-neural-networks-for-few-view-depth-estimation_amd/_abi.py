@@ -286,6 +286,9 @@ SIGNATURES = {
     "cad_unet_get_tensor": (I, [P, I, I, FP, I64]),
     "cad_unet_get_grad": (I, [P, I, FP, I64]),
     "cad_unet_train": (I, [P, I]),
+    "cad_unet_set_fused_eval": (I, [P, I]),
+    "cad_unet_get_fused_eval": (I, [P]),
+    "cad_unet_fused_eval_convs": (I, [P, C.POINTER(I), C.POINTER(I)]),
     "cad_unet_flat": (I, [P, C.POINTER(P), C.POINTER(P), I64P]),
     "cad_unet_use_external_slabs": (I, [P, P, P]),
     "cad_unet_forward": (I, [P, P, P, I, P]),
@@ -365,6 +368,8 @@ SIGNATURES = {
     "cad_op_conv3x3_wgrad_bf16": (I, [P, I64, I, P, I64, I, I, P, I, I, I, P]),
     "cad_op_conv3x3_fwd_bf16": (I, [P, I64, I, I, P, I, P, I64, I, I, I, I, I, I, P]),
     "cad_op_conv3x3_dgrad_bf16": (I, [P, I64, I, P, I, P, I64, I, I, I, I, P]),
+    "cad_op_conv3x3_fwd_act": (I, [P, I64, I, I, P, I, P, P, P, P, P, I64, I, I, I, I, I, P]),
+    "cad_op_conv3x3_fwd_act_bf16": (I, [P, I64, I, I, P, I, P, P, P, P, P, I64, I, I, I, I, I, P]),
     "cad_op_mx8_quantize": (I, [P, I, I64, I, I, I64, P, P, I64, I, P]),
     "cad_op_dense_x8": (I, [P, P, I64, I, P, P, I64, I, P, I64, P]),
     "cad_op_conv3x3_x8": (I, [P, P, I64, I, P, P, I64, I, P, I, I, I, P]),

@@ -82,6 +82,7 @@ struct Args {
     int gpu = 0;
     uint32_t seed = 42;
     bool save_predictions = false, dry_run = false, by_sensor = false, geometry = false;
+    bool fused_forward = false;                  // --fused-forward
     std::vector<float> depth_bins, angle_bins;   // cuts; empty: the option was not given
     std::string stratum;                         // --compare: "depth:2"
     std::vector<NamedView> views;                // --camera-sweep, in command-line order
@@ -111,6 +112,8 @@ void usage() {
                  "                        roll (degrees).  May be repeated\n"
                  "      --view-intrinsics arg  true: the model is given each view's K' (default); source: the\n"
                  "                        sample's own K\n"
+                 "      --fused-forward   Fused eval forward: BatchNorm, ReLU and FiLM in the convolutions' epilogues\n"
+                 "                        (the U-Net families; the same metrics, fewer passes over memory)\n"
                  "      --compare A B     Paired comparison of two per_sample.csv files (no GPU use)\n"
                  "      --stratum arg     With --compare on two per_sample_strata.csv files: axis:bin, e.g. depth:2\n"
                  "      --view arg        With --compare on two per_sample_camera.csv files: axis:value, e.g. zoom:1.5\n"
@@ -219,6 +222,7 @@ Args parse_args(int argc, char** argv) {
         else if (k == "--angle-bins") a.angle_bins = parse_cuts(k, next());
         else if (k == "--by-sensor") a.by_sensor = true;
         else if (k == "--geometry") a.geometry = true;
+        else if (k == "--fused-forward") a.fused_forward = true;
         else if (k == "--camera-sweep") parse_sweep(k, next(), &a.views);
         else if (k == "--view-intrinsics") {
             const std::string m = next();
@@ -725,6 +729,9 @@ int run(const Args& a) {
     check_cut_range("--angle-bins", a.angle_bins, 0.f, 90.f, "degrees");
     const bool geo = c.architecture == "geometry_aware";
     if (geo && pt) throw std::runtime_error("geometry_aware checkpoints are .cadckpt files");
+    if (geo && a.fused_forward)
+        throw std::runtime_error("--fused-forward: model.architecture 'geometry_aware' has no fused eval forward (the "
+                                 "U-Net families baseline_unet, intrinsics_unet, intrinsics_attention_unet, ray_film_unet do)");
     const bool real = c.dataset != "synthetic";
     int64_t ns = a.split == "val" ? c.n_val : c.n_train;
     if (real) {   // the sample count, read on the host before any GPU call
@@ -757,6 +764,8 @@ int run(const Args& a) {
         list("angle_bins", a.angle_bins);
         if (a.by_sensor) std::cout << ", \"by_sensor\": true";
         if (a.geometry) std::cout << ", \"geometry\": true";
+        // (how many convolutions fuse is the handle's to say: cad_unet_fused_eval_convs after a forward)
+        std::cout << ", \"forward\": \"" << (a.fused_forward ? "fused" : "two-pass") << "\"";
         if (!a.views.empty()) {
             std::cout << ", \"camera_sweep\": [";
             for (size_t j = 0; j < a.views.size(); ++j) std::cout << (j ? ", " : "") << "\"" << a.views[j].label << "\"";
@@ -801,6 +810,7 @@ int run(const Args& a) {
         };
     const cad::Workspace ws{c.batch_size, c.height, c.width, a.gpu};
     std::unique_ptr<ModelEvaluator> ev;
+    std::shared_ptr<BaselineUNetImpl> unet;   // the U-Net families: the fused eval forward's switch and count
     if (geo) {
         std::shared_ptr<GeometryAwareNetworkImpl> m;
         if (c.variant == "lightweight") m = std::make_shared<LightweightGeometryNetworkImpl>(3, c.init_features, 4, c.max_depth, ws);
@@ -815,6 +825,8 @@ int run(const Args& a) {
         else m = std::make_shared<BaselineUNetImpl>(3, c.init_features, c.max_depth, ws);
         if (pt) load(*m, a.checkpoint);
         else load_model_state(a.checkpoint, *m);
+        m->fused_eval(a.fused_forward);
+        unet = m;
         ev = std::make_unique<ModelEvaluator>(m, ec);
     }
     std::cout << "Evaluating " << a.checkpoint << " (" << c.architecture << ", f=" << c.init_features << ") on " << ns << " "
@@ -823,6 +835,12 @@ int run(const Args& a) {
               << (a.align != Alignment::None ? std::string(", alignment ") + alignmentName(a.align) : std::string()) << "\n";
     const EvaluationResult r = ev->evaluate(*loader);
     write_outputs(a, c, r);
+    if (unet) {
+        int nf = 0, nt = 0;
+        unet->fused_eval_convs(&nf, &nt);
+        std::cout << "Forward mode: " << (a.fused_forward ? "fused eval forward" : "two-pass eval forward") << ", fused " << nf
+                  << " of " << nt << " convolutions\n";
+    }
     std::cout << "\nMean over " << r.sample_results.size() << " samples:\n" << formatMetrics(r.mean_metrics) << "\nForward: "
               << std::fixed << std::setprecision(3) << r.forward_ms_per_image << " ms per image, " << r.num_parameters
               << " parameters\nResults saved to: " << a.output << "\n";

@@ -51,7 +51,7 @@ struct Args {
     std::vector<std::string> inputs;
     std::vector<int64_t> indices;
     std::vector<float> intrinsics, range;   // fx, fy, cx, cy; lo, hi
-    bool depth_png = false, color_png = false, ply = false, npy = false, panel = false, normals = false, flip_tta = false, dry_run = false;
+    bool depth_png = false, color_png = false, ply = false, npy = false, panel = false, normals = false, flip_tta = false, dry_run = false, fused_forward = false;
     int ply_stride = 1, gpu = 0;
 };
 
@@ -76,6 +76,8 @@ void usage() {
                  "      --colormap arg    jet, hot or gray (default: jet)\n"
                  "      --range lo,hi     Fixed range of the colourised PNG (default: each image's own)\n"
                  "      --flip-tta        Average with the mirrored prediction of the mirrored image\n"
+                 "      --fused-forward   Fused eval forward: BatchNorm, ReLU and FiLM in the convolutions' epilogues\n"
+                 "                        (the U-Net families; the same outputs, fewer passes over memory)\n"
                  "      --gpu arg         GPU ID (default: 0)\n"
                  "      --dry-run         Print the plan and exit; no GPU use\n"
                  "  -h, --help            Print help\n";
@@ -131,6 +133,7 @@ Args parse_args(int argc, char** argv) {
         else if (k == "--colormap") a.colormap = next();
         else if (k == "--range") a.range = split_numbers<float>(next(), "--range");
         else if (k == "--flip-tta") a.flip_tta = true;
+        else if (k == "--fused-forward") a.fused_forward = true;
         else if (k == "--gpu") a.gpu = std::stoi(next());
         else if (k == "--dry-run") a.dry_run = true;
         else throw std::runtime_error("unknown option " + k);
@@ -220,6 +223,9 @@ int run(Args a) {
     if (!a.data_dir.empty()) c.data_dir = a.data_dir;
     const bool geo = c.architecture == "geometry_aware";
     if (geo && pt) throw std::runtime_error("geometry_aware checkpoints are .cadckpt files");
+    if (geo && a.fused_forward)
+        throw std::runtime_error("--fused-forward: model.architecture 'geometry_aware' has no fused eval forward (the "
+                                 "U-Net families baseline_unet, intrinsics_unet, intrinsics_attention_unet, ray_film_unet do)");
     const int cmap = cad::colormap_id(a.colormap);
     if (!a.range.empty() && a.range.size() != 2) throw std::runtime_error("--range takes lo,hi");
     if (a.ply_stride < 1) throw std::runtime_error("--ply-stride must be at least 1");
@@ -291,7 +297,8 @@ int run(Args a) {
                   << a.colormap << "\", \"range\": "
                   << (a.range.empty() ? std::string("null") : "[" + std::to_string(a.range[0]) + ", " + std::to_string(a.range[1]) + "]")
                   << ", \"ply_stride\": " << a.ply_stride << ", \"flip_tta\": " << (a.flip_tta ? "true" : "false")
-                  << ", \"intrinsics\": " << (have_K ? "true" : "false") << "}" << std::endl;
+                  << ", \"intrinsics\": " << (have_K ? "true" : "false") << ", \"forward\": \""
+                  << (a.fused_forward ? "fused" : "two-pass") << "\"}" << std::endl;
         return 0;
     }
 
@@ -321,6 +328,7 @@ int run(Args a) {
         if (pt) load(*unet, a.checkpoint);
         else load_model_state(a.checkpoint, *unet);
         unet->eval();
+        unet->fused_eval(a.fused_forward);
     }
     DeviceTensor rgb = DeviceTensor::empty({B, 3, H, W}, dev), gt = DeviceTensor::empty({B, 1, H, W}, dev),
                  K = DeviceTensor::empty({B, 3, 3}, dev), pred = DeviceTensor::empty({B, 1, H, W}, dev),
@@ -453,6 +461,12 @@ int run(Args a) {
         }
     }
     csv.close();
+    if (unet) {
+        int nf = 0, nt = 0;
+        unet->fused_eval_convs(&nf, &nt);
+        std::cout << "Forward mode: " << (a.fused_forward ? "fused eval forward" : "two-pass eval forward") << ", fused " << nf
+                  << " of " << nt << " convolutions\n";
+    }
     std::cout << "Results saved to: " << a.output << "\n";
     return 0;
 }

@@ -65,6 +65,7 @@ struct Args {
     std::string augmentation;   // --augmentation reference|declared ("" = the config's data.augmentation.mode)
     std::string preview_dir;    // --preview-augmentation DIR: write the first preview_count train samples, no training
     int preview_count = 8;
+    bool fused_validation = false;   // --fused-validation (or validation.fused_forward: true)
     std::vector<std::string> argv;
 };
 
@@ -88,6 +89,9 @@ void usage() {
                  "                        (overrides data.augmentation.mode)\n"
                  "      --preview-augmentation DIR  Write DIR/sample_<i>.png (resized original | augmented) and DIR/draws.csv\n"
                  "                        for the first --preview-count N (default 8) train samples and exit; no training\n"
+                 "      --fused-validation  Validation and the prediction panels run the fused eval forward (BatchNorm, ReLU\n"
+                 "                        and FiLM in the convolutions' epilogues; also validation.fused_forward: true);\n"
+                 "                        the train steps are unchanged.  The U-Net families only\n"
                  "  -h, --help            Print help\n";
 }
 
@@ -120,6 +124,7 @@ Args parse_args(int argc, char** argv) {
             if (a.augmentation != "reference" && a.augmentation != "declared")
                 throw std::runtime_error("--augmentation '" + a.augmentation + "': expected reference or declared");
         }
+        else if (k == "--fused-validation") a.fused_validation = true;
         else if (k == "--preview-augmentation") a.preview_dir = next();
         else if (k == "--preview-count") {
             a.preview_count = std::stoi(next());
@@ -200,6 +205,7 @@ void load_recipe(const yaml_lite::Node& y, Config& c) {
         r.keep_last_n_checkpoints = k["keep_last_n"].as<int>(0);
     }
     if (auto& v = y["validation"]) {
+        r.fused_eval = v["fused_forward"].as<bool>(false);
         r.metric_to_monitor = v["primary_metric"].as<std::string>("abs_rel");
         const std::string& m = r.metric_to_monitor;
         const bool accuracy = m == "a1" || m == "a2" || m == "a3" || m == "delta_1.25";
@@ -570,6 +576,7 @@ int dry_run(const Config& c, const Rank& r, bool tensorboard) {
             o << (e > 1 ? ", " : "") << float_text(TensorBoardTrainerEnhanced::learningRateAt(rc, e));
         o << "]}";
     }
+    if (c.recipe.fused_eval) o << ", \"validation_forward\": \"fused\"";
     o << "}";
     std::cout << o.str() << std::endl;
     if (c.aug_mode == "declared" && r.rank == 0) std::cout << declared_augmentation_text(c) << std::endl;
@@ -655,6 +662,11 @@ int run(const Args& args) {
     c.recipe.learning_rate = c.learning_rate;
     c.recipe.weight_decay = c.weight_decay;
     check_recipe(c);
+    if (args.fused_validation) c.recipe.fused_eval = true;
+    if (c.recipe.fused_eval && c.architecture == "geometry_aware")
+        throw std::runtime_error("validation.fused_forward / --fused-validation: model.architecture 'geometry_aware' has no "
+                                 "fused eval forward (the U-Net families baseline_unet, intrinsics_unet, "
+                                 "intrinsics_attention_unet, ray_film_unet do)");
     if (!args.augmentation.empty()) c.aug_mode = args.augmentation;   // the flag overrides data.augmentation.mode
     load_declared_augmentation(y, c);
     if (c.distributed && c.backend != "nccl" && c.backend != "rccl")
@@ -687,6 +699,7 @@ int run(const Args& args) {
                   << " (warmup " << c.recipe.lr_warmup_epochs << " epochs), ema decay " << c.recipe.ema_decay
                   << ", early stopping " << (c.recipe.use_early_stopping ? "on" : "off") << "\n";
     if (lead && c.aug_mode == "declared") std::cout << declared_augmentation_text(c) << "\n";
+    if (lead && c.recipe.fused_eval) std::cout << "Validation forward mode: fused eval forward\n";
     if (args.debug && lead) std::cout << "Debug mode enabled - using reduced dataset\n";
     int ndev = 0;
     cad::check(cad_device_count(&ndev), "device query");

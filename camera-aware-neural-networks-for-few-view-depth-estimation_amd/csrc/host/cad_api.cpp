@@ -231,6 +231,10 @@ struct cad_unet {
     // the last forward ran decoder level 0's bn2 + ReLU fused with the head (head_fusable): dout[0]
     // was not written, the backward rebuilds the head's input gradient per row
     bool head_fused = false;
+    // cad_unet_set_fused_eval: eval-mode forwards run BatchNorm + ReLU (+ FiLM) in the convolutions' epilogues
+    // (conv3x3_fwd_act; train mode ignores it).  fe_fused of fe_total 3 x 3 convolutions of the last forward did
+    bool fused_eval = false;
+    int fe_fused = 0, fe_total = 0;
     // backward
     float* dcat[4] = {};
     float *Sa = nullptr, *Sb = nullptr, *Sc = nullptr;
@@ -695,26 +699,65 @@ void double_conv_fwd(cad_unet* h, DoubleConv& dc, const float* in, int64_t ldin,
     };
     float* stats = tr ? h->stats : nullptr;
     const bool ps1 = conv1_presplit(h, dc, ps, in_s);
+    // Fused eval forward (cad_unet_set_fused_eval): the BN coefficients come from the running statistics and
+    // gamma / beta from the camera, both before the convolution, and nothing reads the pre-BN output again, so
+    // the convolution's epilogue applies them (EpiStoreAct) and stores what the second pass would have
+    // written.  conv1 always writes exactly one tensor (a1, or its twin on the pre-split engine); an in-loader
+    // conv1 beside pre-split GEMMs (CAD_ENC1PS=0) would need a bf16 store the in-loader kernels are not built
+    // with and stays two-pass.  y1 / y2 are then not written (their debug buffers are stale).
+    const bool fuse = !tr && h->fused_eval;
+    const cad::ActCoeffs act1{dc.b1.scale, dc.b1.shift, dc.has_film() ? dc.film.gam : nullptr,
+                              dc.has_film() ? dc.film.bet : nullptr};
+    h->fe_total += 2;
     // the pre-split (bf16 engine) convolutions store their pre-BN outputs as bf16 (BN statistics are
     // those of the stored values); BN apply / backward and FiLM read them as such
     static const bool enc1_bf16 = env_flag("CAD_ENC1BF16", 0) != 0;
     dc.y1b = ps1 && (!dc.y1_f32 || enc1_bf16);
     dc.y2b = ps;
-    if (ps1) {
-        cad::conv3x3_fwd_ps(in_s, dc.c1.cin, sv(dc.c1.ws, 9 * dc.c1.cin), C, dc.y1, C, 0, B, Hh, Ww, stats, st, dc.y1b);
+    if (fuse && ps1 == ps) {
+        bn(dc.b1, dc.c1.cin, ps1);
+        if (ps1)
+            cad::conv3x3_fwd_ps_act(in_s, dc.c1.cin, sv(dc.c1.ws, 9 * dc.c1.cin), C, dc.a1s, C, 0, B, Hh, Ww, act1, st, true);
+        else
+            cad::conv3x3_fwd_act(in, ldin, 0, dc.c1.cin, h->P(dc.c1.pidx), C, dc.a1, C, 0, B, Hh, Ww, act1, st,
+                                 fwd_wtwin(dc.c1));
+        ++h->fe_fused;
     } else {
-        cad::conv3x3_fwd(in, ldin, 0, dc.c1.cin, h->P(dc.c1.pidx), C, dc.y1, C, 0, B, Hh, Ww, stats, st,
-                         ps ? nullptr : fwd_wtwin(dc.c1));
+        if (ps1) {
+            cad::conv3x3_fwd_ps(in_s, dc.c1.cin, sv(dc.c1.ws, 9 * dc.c1.cin), C, dc.y1, C, 0, B, Hh, Ww, stats, st, dc.y1b);
+        } else {
+            cad::conv3x3_fwd(in, ldin, 0, dc.c1.cin, h->P(dc.c1.pidx), C, dc.y1, C, 0, B, Hh, Ww, stats, st,
+                             ps ? nullptr : fwd_wtwin(dc.c1));
+        }
+        bn(dc.b1, dc.c1.cin, ps1);
+        if (dc.has_film()) {   // FiLMDoubleConvImpl::forward (intrinsics_unet.h:38-52)
+            // pre-split GEMMs read only a1's twin (written by the same pass): the fp32 a1 is not written
+            cad::film_apply(dc.y1, C, dc.b1.scale, dc.b1.shift, dc.film.gam, dc.film.bet, B, (int64_t)Hh * Ww,
+                            ps ? nullptr : dc.a1, st, dc.y1b, ps ? dc.a1s : nullptr);
+        } else {
+            // pre-split GEMMs read only a1's twin (conv2 and its weight gradient): the fp32 a1 is not written
+            cad::bn_relu_fwd(dc.y1, C, dc.b1.scale, dc.b1.shift, ps ? nullptr : dc.a1, C, 0, M, st,
+                             ps ? dc.a1s : nullptr, C, 0, dc.y1b);
+        }
     }
-    bn(dc.b1, dc.c1.cin, ps1);
-    if (dc.has_film()) {   // FiLMDoubleConvImpl::forward (intrinsics_unet.h:38-52)
-        // pre-split GEMMs read only a1's twin (written by the same pass): the fp32 a1 is not written
-        cad::film_apply(dc.y1, C, dc.b1.scale, dc.b1.shift, dc.film.gam, dc.film.bet, B, (int64_t)Hh * Ww,
-                        ps ? nullptr : dc.a1, st, dc.y1b, ps ? dc.a1s : nullptr);
-    } else {
-        // pre-split GEMMs read only a1's twin (conv2 and its weight gradient): the fp32 a1 is not written
-        cad::bn_relu_fwd(dc.y1, C, dc.b1.scale, dc.b1.shift, ps ? nullptr : dc.a1, C, 0, M, st, ps ? dc.a1s : nullptr,
-                         C, 0, dc.y1b);
+    // conv2 fused: not when its y2 feeds a fused head, and not when the second pass writes both an fp32 tensor
+    // and a twin; an encoder block's max-pool is then the caller's separate pass (pool == nullptr)
+    {
+        const bool twin = ps && out_s.p;
+        const bool f32 = out_f32 || !twin;
+        if (fuse && !head_pred && !pool && !(twin && f32)) {
+            const cad::ActCoeffs act2{dc.b2.scale, dc.b2.shift, nullptr, nullptr};
+            bn(dc.b2, C, ps);
+            if (ps)
+                cad::conv3x3_fwd_ps_act(sv(dc.a1s, C), C, sv(dc.c2.ws, 9 * C), C,
+                                        twin ? const_cast<void*>(out_s.p) : static_cast<void*>(out),
+                                        twin ? out_s.ld : ldo, twin ? out_s.coff : ocoff, B, Hh, Ww, act2, st, twin);
+            else
+                cad::conv3x3_fwd_act(dc.a1, C, 0, C, h->P(dc.c2.pidx), C, out, ldo, ocoff, B, Hh, Ww, act2, st,
+                                     fwd_wtwin(dc.c2));
+            ++h->fe_fused;
+            return;
+        }
     }
     if (ps)
         cad::conv3x3_fwd_ps(sv(dc.a1s, C), C, sv(dc.c2.ws, 9 * C), C, dc.y2, C, 0, B, Hh, Ww, stats, st, true);
@@ -797,7 +840,9 @@ void unet_forward(cad_unet* h, const float* rgb, const float* cam4, float* depth
         const bool ptwin = ps && h->pools[l];
         return PoolOut{ptwin ? nullptr : h->pool[l], h->pidx[l], ptwin ? h->pools[l] : nullptr};
     };
-    const bool fuse_pool = bn_pool_on();
+    // (the fused eval forward stores the encoder outputs from conv2's epilogue: the max-pool is its own pass)
+    const bool fuse_pool = bn_pool_on() && !(h->fused_eval && !h->train);
+    h->fe_fused = h->fe_total = 0;
     PoolOut po = pool_of(1);
     double_conv_fwd(h, h->enc[0], h->x0, h->x0_ld, x0s, B, h->cat[0], 2 * f, 0, sv(h->cats[0], 2 * f), st, !ps, nullptr,
                     fuse_pool ? &po : nullptr);
@@ -1422,6 +1467,21 @@ cad_status cad_unet_histograms(cad_unet* h, int which, void* stream, cad_hist** 
 
 cad_status cad_unet_train(cad_unet* h, int train) {
     return guard([&] { h->train = train != 0; });
+}
+
+cad_status cad_unet_set_fused_eval(cad_unet* h, int on) {
+    return guard([&] {
+        require(h != nullptr, "null handle");
+        h->fused_eval = on != 0;
+    });
+}
+int cad_unet_get_fused_eval(const cad_unet* h) { return h && h->fused_eval ? 1 : 0; }
+cad_status cad_unet_fused_eval_convs(const cad_unet* h, int* fused, int* total) {
+    return guard([&] {
+        require(h != nullptr, "null handle");
+        if (fused) *fused = h->fe_fused;
+        if (total) *total = h->fe_total;
+    });
 }
 
 cad_status cad_unet_flat(cad_unet* h, float** params, float** grads, int64_t* n) {
@@ -2972,6 +3032,58 @@ cad_status cad_op_conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, c
         }
         cad::conv3x3_fwd(x, ldx, xcoff, cin, w, cout, y, ldy, ycoff, B, H, W, nullptr, S(stream), twin);
         if (twin) HIPCHK(hipFreeAsync(twin, S(stream)));
+        HIPCHK(hipGetLastError());
+    });
+}
+namespace {
+void act_require(const float* scale, const float* shift, const float* gam, const float* bet, int y_bf16, int B, int H,
+                 int W) {
+    require(scale && shift, "null scale / shift");
+    require((gam == nullptr) == (bet == nullptr), "gamma and beta: both or neither");
+    require(y_bf16 == 0 || y_bf16 == 1, "y_bf16 must be 0 or 1");
+    require(B > 0 && H > 0 && W > 0 && ((int64_t)H * W) % 4 == 0, "B, H, W > 0 and H * W a multiple of 4");
+}
+}  // namespace
+cad_status cad_op_conv3x3_fwd_act(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout,
+                                  const float* scale, const float* shift, const float* gam, const float* bet, void* y,
+                                  int64_t ldy, int ycoff, int y_bf16, int B, int H, int W, void* stream) {
+    return guard([&] {
+        require(x && w && y, "null argument");
+        act_require(scale, shift, gam, bet, y_bf16, B, H, W);
+        require(y_bf16 == 0, "bf16 output is the pre-split entry's (cad_op_conv3x3_fwd_act_bf16): fp32 operands store fp32");
+        require(cin > 0 && cout > 0 && cin % 4 == 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && xcoff % 4 == 0 &&
+                    ycoff % 4 == 0 && xcoff >= 0 && ycoff >= 0 && ldx >= xcoff + cin && ldy >= ycoff + cout,
+                "channels / strides must be multiples of 4 and the views must fit their rows");
+        void* twin = nullptr;
+        const int bn = cad::conv3x3_wtwin_on() ? cad::conv3x3_wtwin_bn(cin, W, cout) : 0;
+        if (bn) {
+            HIPCHK(hipMallocAsync(&twin, (size_t)cad::conv3x3_wtwin_bytes(cin, cout), S(stream)));
+            cad::WPrepList L{};
+            wprep_twin_add(L, cad::WPREP_WTWIN_FWD, w, twin, cout, cin, bn);
+            cad::weight_prep(L, S(stream));
+        }
+        cad::conv3x3_fwd_act(x, ldx, xcoff, cin, w, cout, static_cast<float*>(y), ldy, ycoff, B, H, W,
+                             cad::ActCoeffs{scale, shift, gam, bet}, S(stream), twin);
+        if (twin) HIPCHK(hipFreeAsync(twin, S(stream)));
+        HIPCHK(hipGetLastError());
+    });
+}
+cad_status cad_op_conv3x3_fwd_act_bf16(const void* x, int64_t ldx, int xcoff, int cin, const float* w, int cout,
+                                       const float* scale, const float* shift, const float* gam, const float* bet,
+                                       void* y, int64_t ldy, int ycoff, int y_bf16, int B, int H, int W, void* stream) {
+    return guard([&] {
+        require(x && w && y, "null argument");
+        act_require(scale, shift, gam, bet, y_bf16, B, H, W);
+        require(cin > 0 && cout > 0 && cin % 8 == 0 && xcoff % 8 == 0 && ldx % 8 == 0 && xcoff >= 0 && ycoff >= 0 &&
+                    ldx >= xcoff + cin && ldy >= ycoff + cout && cout % 4 == 0,
+                "bad arguments (bf16 rows: ldx, xcoff, cin multiples of 8; the views must fit their rows)");
+        require(cad::gemm_engine() == 2, "the pre-split convolution runs on the bf16 engine (CAD_GEMM_BF16)");
+        void* ws = nullptr;
+        HIPCHK(hipMallocAsync(&ws, sizeof(uint16_t) * (size_t)cout * 9 * cin, S(stream)));
+        cad::split_rows(w, 9 * cin, 0, 9 * cin, cout, ws, 9 * cin, 0, S(stream));
+        cad::conv3x3_fwd_ps_act(cad::Split{x, ldx, xcoff}, cin, cad::Split{ws, 9 * cin, 0}, cout, y, ldy, ycoff, B, H, W,
+                                cad::ActCoeffs{scale, shift, gam, bet}, S(stream), y_bf16 != 0);
+        HIPCHK(hipFreeAsync(ws, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }

@@ -432,6 +432,22 @@ CAD_NP_KT(s3, 3)
 CAD_NP_KT(bf16, B)
 CAD_NP_KT(bf16p, P1)
 #undef CAD_NP_KT
+// the im2col forwards with the eval-mode activation epilogue (EpiStoreAct<bf16 output, FiLM>): KConvFwdAct<F>
+// (f32), ...3 (S3), ...B (B1 in-loader), ...P1 (B1 pre-split; O = bf16 output)
+#define CAD_ACT_KT(NAME, KERN, OB, FI)                             \
+    CAD_KT(NAME, (KERN<WM, WN, KB, EpiStoreAct<OB, FI>>),          \
+           "void cad::" #KERN "<%d, %d, %d, cad::EpiStoreAct<" #OB ", " #FI ">>(cad::GemmArgs)")
+CAD_ACT_KT(KConvFwdAct, k_conv3x3_fwd, false, false)
+CAD_ACT_KT(KConvFwdActF, k_conv3x3_fwd, false, true)
+CAD_ACT_KT(KConvFwdAct3, k_conv3x3_fwd_s3, false, false)
+CAD_ACT_KT(KConvFwdActF3, k_conv3x3_fwd_s3, false, true)
+CAD_ACT_KT(KConvFwdActB, k_conv3x3_fwd_bf16, false, false)
+CAD_ACT_KT(KConvFwdActFB, k_conv3x3_fwd_bf16, false, true)
+CAD_ACT_KT(KConvFwdActP1, k_conv3x3_fwd_bf16p, false, false)
+CAD_ACT_KT(KConvFwdActFP1, k_conv3x3_fwd_bf16p, false, true)
+CAD_ACT_KT(KConvFwdActOP1, k_conv3x3_fwd_bf16p, true, false)
+CAD_ACT_KT(KConvFwdActFOP1, k_conv3x3_fwd_bf16p, true, true)
+#undef CAD_ACT_KT
 #undef CAD_KT
 
 // `splits` launches of one contraction on the current engine with in-loader operand conversion:
@@ -478,6 +494,15 @@ WinPick pick_win_shape(int cin, int W, int N) {
 }
 WinPick pick_win(int cin, int W, int N) { return engine() == 1 ? pick_win_shape(cin, W, N) : WinPick{}; }
 int win_blocks(const WinPick& w, int B, int H, int W) { return B * cdiv(H, w.R) * (W / w.CW); }
+// the profiler's name of a plain-store or activation epilogue (EpiStoreAct<bf16 output, FiLM>)
+template <class Epi>
+const char* act_name() {
+    if constexpr (is_act<Epi>::value)
+        return Epi::BF16 ? (Epi::FILM ? "EpiStoreAct<true, true>" : "EpiStoreAct<true, false>")
+                         : (Epi::FILM ? "EpiStoreAct<false, true>" : "EpiStoreAct<false, false>");
+    else
+        return "EpiStore";
+}
 // PS = false: S3 window kernel (fp32 operands, in-loader split); true: B1 on the pre-split twins
 template <bool PS, int R, int CW, class Epi, bool BIG = false, bool N96 = false>
 void launch_win1(const GemmArgs& a, hipStream_t st) {
@@ -493,8 +518,8 @@ void launch_win1(const GemmArgs& a, hipStream_t st) {
         char name[160];
         snprintf(name, sizeof(name), "void cad::k_conv3x3_win_%s<%d, %d, cad::%s%s%s>(cad::GemmArgs)",
                  N96 ? "bf16p3" : BIG ? "bf16p4" : PS ? "bf16p" : "s3", R, CW,
-                 Epi::STATS ? "EpiStoreStats" : is_bnsums<Epi>::value ? "EpiStoreBnSums" : "EpiStore",
-                 Epi::BF16 ? "B16" : "", !PS && !N96 && !BIG && a.wtwin ? ", true" : "");
+                 Epi::STATS ? "EpiStoreStats" : is_bnsums<Epi>::value ? "EpiStoreBnSums" : act_name<Epi>(),
+                 Epi::BF16 && !is_act<Epi>::value ? "B16" : "", !PS && !N96 && !BIG && a.wtwin ? ", true" : "");
         prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
         hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
         prof_pop(st);
@@ -886,6 +911,44 @@ void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w
     else launch_engine<KConvFwd, KConvFwd3, KConvFwdB>(c, true, a, st);
 }
 
+namespace {
+void act_check(const ActCoeffs& act, int H, int W) {
+    if (!act.scale || !act.shift || !act.gam != !act.bet) throw std::invalid_argument("conv3x3_fwd_act: coefficient pointers");
+    // the row-major epilogue takes a 4-row group's sample from its first row
+    if ((int64_t)H * W % 4) throw std::invalid_argument("conv3x3_fwd_act: H * W must be a multiple of 4");
+}
+void act_args(GemmArgs& a, const ActCoeffs& act) {
+    a.bn_scale = act.scale; a.bn_shift = act.shift; a.act_gam = act.gam; a.act_bet = act.bet;
+}
+}  // namespace
+
+void conv3x3_fwd_act(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y, int64_t ldy,
+                     int ycoff, int B, int H, int W, const ActCoeffs& act, hipStream_t st, const void* wtwin) {
+    act_check(act, H, W);
+    CAD_NO_ALIAS("conv3x3_fwd_act", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, 4, "y")},
+                 {aview(x, (int64_t)B * H * W, ldx, xcoff, cin, 4, "x"), aview(w, cout, 9 * cin, 0, 9 * cin, 4, "w"),
+                  aview(wtwin, 1, conv3x3_wtwin_bytes(cin, cout), 0, wtwin ? conv3x3_wtwin_bytes(cin, cout) : 0, 1, "wtwin"),
+                  aview(act.scale, 1, cout, 0, cout, 4, "scale"), aview(act.shift, 1, cout, 0, cout, 4, "shift"),
+                  aview(act.gam, B, cout, 0, act.gam ? cout : 0, 4, "gamma"),
+                  aview(act.bet, B, cout, 0, act.bet ? cout : 0, 4, "beta")});
+    GemmArgs a{};
+    a.M = B * H * W; a.N = cout; a.K = 9 * cin;
+    a.B = B; a.H = H; a.W = W;
+    a.A = x; a.lda = ldx; a.a_coff = xcoff; a.a_cin = cin;
+    a.Bm = w; a.ldb = 9 * cin; a.b_coff = 0;
+    a.C = y; a.ldc = ldy; a.c_coff = ycoff;
+    act_args(a, act);
+    if (const WinPick wp = pick_win(cin, W, cout); wp.R) {
+        a.wtwin = wtwin;
+        if (act.gam) launch_win<EpiStoreAct<false, true>>(wp, a, st);
+        else launch_win<EpiStoreAct<false, false>>(wp, a, st);
+        return;
+    }
+    const Cfg c = pick_cfg(a.M, a.N);
+    if (act.gam) launch_engine<KConvFwdActF, KConvFwdActF3, KConvFwdActFB>(c, true, a, st);
+    else launch_engine<KConvFwdAct, KConvFwdAct3, KConvFwdActB>(c, true, a, st);
+}
+
 void convT_fwd(const float* x, int64_t ldx, int cin, const float* wf, const float* bias, int cout,
                float* y, int64_t ldy, int ycoff, int B, int H, int W, hipStream_t st) {
     CAD_NO_ALIAS("convT_fwd", {aview(y, (int64_t)B * 4 * H * W, ldy, ycoff, cout, 4, "y")},
@@ -1027,6 +1090,47 @@ void conv3x3_fwd_ps(Split x, int cin, Split w, int cout, float* y, int64_t ldy, 
     } else {
         if (stats) launch_kb<KConvFwdSP1, 32, 64>(c, kb, a, 1, st);
         else launch_kb<KConvFwdP1, 32, 64>(c, kb, a, 1, st);
+    }
+}
+
+void conv3x3_fwd_ps_act(Split x, int cin, Split w, int cout, void* y, int64_t ldy, int ycoff, int B, int H, int W,
+                        const ActCoeffs& act, hipStream_t st, bool y_bf16) {
+    ps_check(x, cin, "conv3x3_fwd_act x");
+    ps_check(w, 9 * cin, "conv3x3_fwd_act w");
+    act_check(act, H, W);
+    CAD_NO_ALIAS("conv3x3_fwd_ps_act", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, y_bf16 ? 2 : 4, "y")},
+                 {aview(x.p, (int64_t)B * H * W, x.ld, x.coff, cin, 2, "x"), aview(w.p, cout, w.ld, w.coff, 9 * cin, 2, "w"),
+                  aview(act.scale, 1, cout, 0, cout, 4, "scale"), aview(act.shift, 1, cout, 0, cout, 4, "shift"),
+                  aview(act.gam, B, cout, 0, act.gam ? cout : 0, 4, "gamma"),
+                  aview(act.bet, B, cout, 0, act.bet ? cout : 0, 4, "beta")});
+    GemmArgs a{};
+    a.M = B * H * W; a.N = cout; a.K = 9 * cin;
+    a.B = B; a.H = H; a.W = W;
+    a.A = (const float*)x.p; a.lda = x.ld; a.a_coff = x.coff; a.a_cin = cin;
+    a.Bm = (const float*)w.p; a.ldb = w.ld; a.b_coff = w.coff;
+    a.C = static_cast<float*>(y); a.ldc = ldy; a.c_coff = ycoff;
+    act_args(a, act);
+    const bool film = act.gam != nullptr;
+    if (const WinPick wp = pick_win_ps(cin, W, cout, x.coff); wp.R && w.coff == 0) {
+        if (y_bf16) {
+            if (film) launch_win<EpiStoreAct<true, true>, true>(wp, a, st);
+            else launch_win<EpiStoreAct<true, false>, true>(wp, a, st);
+        } else {
+            if (film) launch_win<EpiStoreAct<false, true>, true>(wp, a, st);
+            else launch_win<EpiStoreAct<false, false>, true>(wp, a, st);
+        }
+        return;
+    }
+    const Cfg c = pick_cfg(a.M, a.N);
+    const int kb = ps_kb(true, c);
+    a.kstages_per_split = cdiv(a.K, kb);
+    a.cimajor = cin % kb == 0;
+    if (y_bf16) {
+        if (film) launch_kb<KConvFwdActFOP1, 32, 64>(c, kb, a, 1, st);
+        else launch_kb<KConvFwdActOP1, 32, 64>(c, kb, a, 1, st);
+    } else {
+        if (film) launch_kb<KConvFwdActFP1, 32, 64>(c, kb, a, 1, st);
+        else launch_kb<KConvFwdActP1, 32, 64>(c, kb, a, 1, st);
     }
 }
 

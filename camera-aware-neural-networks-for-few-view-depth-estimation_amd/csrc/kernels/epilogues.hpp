@@ -82,6 +82,28 @@ struct EpiStoreBnSums {
     static constexpr bool Y_BF16 = YB;
 };
 
+// Eval-mode forward ("Fused eval forward"): the BatchNorm affine, the ReLU and, with FILM, the
+// FiLM modulation of the block, applied to the finished accumulator, so the convolution stores the
+// activation and its pre-BN output never reaches memory.  For value v in column n of sample b:
+//   o = max(fma(v, bn_scale[n], bn_shift[n]), 0)                             (bn_relu1, nn_kernels.hip)
+//   o = act_gam[b][n] * max(v * bn_scale[n] + bn_shift[n], 0) + act_bet[b][n]  (k_film_apply, film_kernels.hip)
+// in fp32, then stored as fp32 or (OB16) rounded once to bf16.  The coefficients exist before the launch
+// (bn_eval_coeffs, film_mlp_fwd_all): a lane fetches them once per column block (ActCoef, gemm_mfma.hpp).
+// Served by all three epilogue bodies (gemm_epilogue_t, win_epilogue, win_epilogue16); no BN partials.
+template <bool OB16, bool FILM_>
+struct EpiStoreAct {
+    static constexpr bool STATS = false;
+    static constexpr bool BF16 = OB16;
+    static constexpr bool ADD = false;
+    static constexpr bool SPLIT = false;
+    static constexpr bool ACT = true;
+    static constexpr bool FILM = FILM_;
+    __device__ static const float* row_base(const GemmArgs& a, int m0, int z) {
+        if constexpr (OB16) return EpiStoreB16::row_base(a, m0, z);
+        else return EpiStore::row_base(a, m0, z);
+    }
+};
+
 // ConvTranspose2d(k2,s2) pixel shuffle: n = (q=(dy,dx), co) -> high-res pixel (2y+dy, 2x+dx).
 // The column (q, co) is fixed per lane and sub-block (STRUCTURED epilogue).  When W % 32 == 0 a
 // 32-row block is one run of 32 pixels of one image row (blocks start at multiples of 32), so its

@@ -72,6 +72,9 @@ struct GemmArgs {
     // conv3x3 window kernels on the S3 engine: the weights' three-plane twin in LDS-image order
     // (gemm_win.hpp WinTwinGeo), or nullptr for the in-loader split of Bm
     const void* wtwin;
+    // EpiStoreAct (epilogues.hpp): the FiLM modulation gamma / beta [B][N] applied after bn_scale / bn_shift and
+    // the ReLU (read only by the FILM instantiations)
+    const float *act_gam, *act_bet;
 };
 
 
@@ -454,6 +457,46 @@ struct is_bnsums : std::false_type {};   // EpiStoreBnSums (epilogues.hpp)
 template <class E>
 struct is_bnsums<E, std::void_t<decltype(E::BNSUMS)>> : std::integral_constant<bool, E::BNSUMS> {};
 template <class E, class = void>
+struct is_act : std::false_type {};   // EpiStoreAct (epilogues.hpp)
+template <class E>
+struct is_act<E, std::void_t<decltype(E::ACT)>> : std::integral_constant<bool, E::ACT> {};
+template <class E>
+constexpr bool epi_film() {
+    if constexpr (is_act<E>::value) return E::FILM;
+    else return false;
+}
+// EpiStoreAct's arithmetic on one accumulator value: the eval-mode BatchNorm + ReLU as bn_relu1
+// (nn_kernels.hip) forms it, and the FiLM affine spelled as k_film_apply (film_kernels.hip) spells it, so
+// the compiler contracts both the same way and the fused forward keeps the two-pass forward's bits
+__device__ __forceinline__ float act_bn_relu(float v, float s, float t) { return fmaxf(__fmaf_rn(v, s, t), 0.f); }
+__device__ __forceinline__ float act_film(float v, float s, float t, float g, float b) {
+    return g * fmaxf(v * s + t, 0.f) + b;
+}
+// a lane's BN coefficients (and, in a window kernel where the sample b is uniform, its FiLM gamma / beta) for
+// its NB column blocks of CB columns starting at column ncol0: loaded once per block, not per element
+template <int NB, int CB, bool FILM>
+struct ActCoef {
+    float sc[NB], sh[NB], g[FILM ? NB : 1], be[FILM ? NB : 1];
+    __device__ __forceinline__ void init(const GemmArgs& a, int ncol0, int b) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int n = min(ncol0 + j * CB, a.N - 1);
+            sc[j] = a.bn_scale[n];
+            sh[j] = a.bn_shift[n];
+            if constexpr (FILM) {
+                if (b >= 0) {
+                    g[j] = a.act_gam[(int64_t)b * a.N + n];
+                    be[j] = a.act_bet[(int64_t)b * a.N + n];
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ float operator()(int j, float v) const {
+        if constexpr (FILM) return act_film(v, sc[j], sh[j], g[j], be[j]);
+        else return act_bn_relu(v, sc[j], sh[j]);
+    }
+};
+template <class E, class = void>
 struct is_structured : std::false_type {};
 template <class E>
 struct is_structured<E, std::void_t<decltype(E::STRUCTURED)>> : std::integral_constant<bool, E::STRUCTURED> {};
@@ -699,6 +742,13 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& a, const floatx1
                                             lds + wave * Epi::template lds_floats_per_wave<NJ>()))
             return;
     }
+    constexpr bool ACT = is_act<Epi>::value, FILM = epi_film<Epi>();
+    [[maybe_unused]] ActCoef<ACT ? NJ : 1, 32, false> act;   // (FiLM: gamma / beta per 4-row group below)
+    [[maybe_unused]] int hw = 1;
+    if constexpr (ACT) {
+        act.init(a, n0 + wn * 32 * NJ + (lane & 31), -1);
+        hw = a.H * a.W;
+    }
     // one memory round trip for the whole tile instead of one per block
     if constexpr (has_prefetch<Epi>::value)
         epi.template prefetch<MI, NJ>(a, m0 + wm * 32 * MI + 4 * (lane >> 5), n0 + wn * 32 * NJ + (lane & 31));
@@ -740,6 +790,19 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& a, const floatx1
                                                                            rsmask, lo + (uint32_t)(r * ldc4), 0, 0));
                             v[r] = mk > 0.f ? v[r] : 0.f;
                         }
+                    }
+                }
+                if constexpr (ACT) {
+                    if constexpr (FILM) {
+                        // the group's four rows lie in one sample (H W % 4 == 0); rows past M are clamped
+                        // (their stores are dropped) and columns past N read the last column's constants
+                        const int b = min((m0 + mr) / hw, a.B - 1), nn = min(n, a.N - 1);
+                        const float gm = a.act_gam[(int64_t)b * a.N + nn], bt = a.act_bet[(int64_t)b * a.N + nn];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = act_film(v[r], act.sc[j], act.sh[j], gm, bt);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = act(j, v[r]);
                     }
                 }
                 if constexpr (Epi::BF16) {   // the stored (rounded) values, which BN then normalises

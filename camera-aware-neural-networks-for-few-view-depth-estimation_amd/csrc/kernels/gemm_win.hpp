@@ -261,6 +261,9 @@ __device__ __forceinline__ void win_epilogue(const GemmArgs& a, const floatx16 (
     constexpr bool BNS = is_bnsums<Epi>::value;
     [[maybe_unused]] WinBnSums<BNS ? NJ : 1, 32, epi_y_bf16<Epi>()> bns;
     if constexpr (BNS) bns.init(a, b, y0, x0, n0 + wn * 32 * NJ + (lane & 31));
+    constexpr bool ACT = is_act<Epi>::value;   // (a workgroup owns one image: the sample b is uniform)
+    [[maybe_unused]] ActCoef<ACT ? NJ : 1, 32, epi_film<Epi>()> act;
+    if constexpr (ACT) act.init(a, n0 + wn * 32 * NJ + (lane & 31), b);
     constexpr int ES = Epi::BF16 ? 2 : 4;   // output element bytes
     const int64_t ldc4 = a.ldc * ES;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(reinterpret_cast<const float*>(
@@ -286,6 +289,10 @@ __device__ __forceinline__ void win_epilogue(const GemmArgs& a, const floatx16 (
                 float v[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = acc[i][j][4 * g + q];
+                if constexpr (ACT) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = act(j, v[q]);
+                }
                 if constexpr (Epi::BF16) {   // the stored (rounded) values, which BN then normalises
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[q] = (float)(__bf16)v[q];
@@ -348,6 +355,9 @@ __device__ __forceinline__ void win_epilogue16(const GemmArgs& a, const floatx4 
     constexpr bool BNS = is_bnsums<Epi>::value;
     [[maybe_unused]] WinBnSums<BNS ? NB : 1, 16, epi_y_bf16<Epi>()> bns;
     if constexpr (BNS) bns.init(a, b, y0, x0, n0 + wn * 16 * NB + (lane & 15));
+    constexpr bool ACT = is_act<Epi>::value;
+    [[maybe_unused]] ActCoef<ACT ? NB : 1, 16, epi_film<Epi>()> act;
+    if constexpr (ACT) act.init(a, n0 + wn * 16 * NB + (lane & 15), b);
     constexpr int ES = Epi::BF16 ? 2 : 4;
     const int64_t ldc4 = a.ldc * ES;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(reinterpret_cast<const float*>(
@@ -370,6 +380,10 @@ __device__ __forceinline__ void win_epilogue16(const GemmArgs& a, const floatx4 
             float v[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = acc[i][j][q];
+            if constexpr (ACT) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = act(j, v[q]);
+            }
             if constexpr (Epi::BF16) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = (float)(__bf16)v[q];

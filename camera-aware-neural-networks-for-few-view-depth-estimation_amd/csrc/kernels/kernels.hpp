@@ -55,6 +55,21 @@ int gemm_engine();
 // kernels do not serve: the in-loader split.  Same bits either way.
 void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y,
                  int64_t ldy, int ycoff, int B, int H, int W, float* stats, hipStream_t st, const void* wtwin = nullptr);
+// The eval-mode forward's fused convolutions (EpiStoreAct, epilogues.hpp): conv3x3_fwd / conv3x3_fwd_ps with the
+// block's BatchNorm + ReLU and, when gam / bet are given, its FiLM modulation applied in the GEMM epilogue:
+//   y[p][n] = max(fma(conv, scale[n], shift[n]), 0)                      gam == nullptr
+//   y[p][n] = gam[b][n] * max(conv * scale[n] + shift[n], 0) + bet[b][n]  b = p / (H W)
+// scale / shift: cout floats (bn_eval_coeffs); gam / bet: [B][cout] (film_mlp_fwd_all), both or neither.  The
+// pre-BN convolution output is not written; there are no BN partials.  H W % 4 == 0.
+struct ActCoeffs {
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+    const float* gam = nullptr;
+    const float* bet = nullptr;
+};
+// fp32 operands on the current engine (window kernels where conv3x3_fwd takes them), fp32 y
+void conv3x3_fwd_act(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y, int64_t ldy,
+                     int ycoff, int B, int H, int W, const ActCoeffs& act, hipStream_t st, const void* wtwin = nullptr);
 // Weight twin of a 3 x 3 convolution for the S3 window kernels: the three bf16 planes of split3 of
 // Wt[n][tap * cin + ci] (forward: n = cout, the OHWI parameters; dgrad: the repack, n and cin swapped) in
 // the kernels' LDS-image order, one 9 * bn * 32-byte block per (N tile of bn rows, stage (cb, ky)):
@@ -100,6 +115,10 @@ void split_rows(const float* x, int64_t ldx, int xcoff, int C, int64_t M, void* 
 // y_bf16: y is written as bf16 rows of ldy elements (the bf16 engine's pre-BN outputs)
 void conv3x3_fwd_ps(Split x, int cin, Split w, int cout, float* y, int64_t ldy, int ycoff, int B, int H, int W,
                     float* stats, hipStream_t st, bool y_bf16 = false);
+// ... on the pre-split twins (bf16 engine); y: fp32 rows, or with y_bf16 bf16 rows (the consumer's twin),
+// rounded once from the fp32 activation
+void conv3x3_fwd_ps_act(Split x, int cin, Split w, int cout, void* y, int64_t ldy, int ycoff, int B, int H, int W,
+                        const ActCoeffs& act, hipStream_t st, bool y_bf16);
 // dx_bf16: dx is written as bf16 rows of lddx elements (the bf16 engine's conv2 input gradient).
 // hi != nullptr: columns [split_n, cin) go to the bf16 rows hi (ldhi elements) instead of dx when the
 // window kernel runs and split_n % 32 == 0 (returns true); otherwise all of dx is written as fp32

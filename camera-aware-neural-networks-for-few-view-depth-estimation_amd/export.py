@@ -91,9 +91,13 @@ class Predictor:
     model may be None for an exporter without a network (colorize / to_uint16 / points of any depth map of
     that size).  Every method enqueues on the current stream; nothing is copied to the host."""
 
-    def __init__(self, model, batch: int, height: int, width: int, device: int | None = None):
+    def __init__(self, model, batch: int, height: int, width: int, device: int | None = None, fused_eval=None):
+        """fused_eval (None: leave the model's switch): predict with the fused eval forward (model.fused_eval)."""
         import torch
         self.lib = _abi.load()
+        if model is not None:
+            from . import model as M
+            M._set_fused_eval(model, fused_eval)
         self.model, self.batch, self.height, self.width = model, int(batch), int(height), int(width)
         dev = device if device is not None else (model.device.index if model is not None else 0)
         self.device = torch.device("cuda", dev or 0)

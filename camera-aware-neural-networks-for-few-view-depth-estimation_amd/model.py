@@ -117,6 +117,22 @@ class BaselineUNet:
     def eval(self):
         return self.train(False)
 
+    def fused_eval(self, on=True):
+        """Fused eval forward (cad_unet_set_fused_eval; off by default): eval-mode forwards apply each block's
+        BatchNorm + ReLU (+ FiLM) in the 3 x 3 convolutions' epilogues, so the pre-BN outputs are never written.
+        Train-mode forwards ignore it.  fp32 engines: the same bits; bf16 engine: one rounding instead of two."""
+        check(self.lib.cad_unet_set_fused_eval(self.h, int(bool(on))), "cad_unet_set_fused_eval")
+        return self
+
+    def fused_eval_on(self) -> bool:
+        return bool(self.lib.cad_unet_get_fused_eval(self.h))
+
+    def fused_eval_convs(self):
+        """(fused, total): how many of the last forward's 3 x 3 convolutions ran the fused epilogue."""
+        a, b = C.c_int(), C.c_int()
+        check(self.lib.cad_unet_fused_eval_convs(self.h, C.byref(a), C.byref(b)), "cad_unet_fused_eval_convs")
+        return a.value, b.value
+
     def count_parameters(self) -> int:
         return int(self.lib.cad_unet_count_parameters(self.h))
 
@@ -856,8 +872,21 @@ def camera_view(rgb, depth, K, view=None, K_new=None, R=None, mask=None, out=Non
     return rgb_o, depth_o, K_new, valid.bool()
 
 
+def _set_fused_eval(model, fused_eval):
+    """Apply a fused_eval= argument (None: leave the model's switch as it is); a model family without the fused
+    eval forward refuses True."""
+    if fused_eval is None:
+        return
+    if not hasattr(model, "fused_eval"):
+        if fused_eval:
+            raise ValueError(f"{type(model).__name__} has no fused eval forward (the U-Net families only)")
+        return
+    model.fused_eval(fused_eval)
+
+
 def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, keep_predictions=False, align="none",
-             depth_bins=None, angle_bins=None, geometry=False, camera_sweep=None, view_intrinsics="true"):
+             depth_bins=None, angle_bins=None, geometry=False, camera_sweep=None, view_intrinsics="true",
+             fused_eval=None):
     """ModelEvaluator: eval-mode forwards over `batches` of (rgb, gt, K[, mask]) device tensors, every
     prediction scored on device (Evaluator.update) with no host synchronisation inside the loop; the
     model's train / eval mode is restored.  Returns {"keys", "per_sample" (N,12), "summary",
@@ -871,8 +900,11 @@ def evaluate(model, batches, min_depth=0.1, max_depth=10.0, clamp_pred=True, kee
     list of {"label", "view", "per_sample" (N,12), "summary", "alignment", "aligned", "valid_share" (the view's
     valid pixels over the main pass's)}.  view_intrinsics="true": the model is given each view's K';
     "source": the sample's own K, while the data is still the warped one (how much does the model rely on
-    K?).  Strata and geometry are not computed per view; "forward_ms_per_image" stays the main pass's."""
+    K?).  Strata and geometry are not computed per view; "forward_ms_per_image" stays the main pass's.
+    fused_eval (None: the model's own switch): run the forwards with the fused eval forward on / off
+    (BaselineUNet.fused_eval); the switch keeps the value."""
     _abi.eval_align_mode(align)
+    _set_fused_eval(model, fused_eval)
     if view_intrinsics not in ("true", "source"):
         raise ValueError(f"view_intrinsics must be 'true' or 'source', not {view_intrinsics!r}")
     if camera_sweep is None:
@@ -1074,11 +1106,15 @@ class Trainer:
 
     def __init__(self, model: BaselineUNet, loss_fn: CombinedDepthLoss, lr=1e-4, weight_decay=1e-5,
                  grad_clip=1.0, use_grad_clip=True, process_group=None, bucket_mb=25.0, communicator=None,
-                 optimizer="adam", schedule=None, ema_decay=0.0, momentum=0.0, betas=(0.9, 0.999), eps=1e-8):
-        """optimizer / schedule / ema_decay are the declared recipe (off by default: the reference's Adam at a
+                 optimizer="adam", schedule=None, ema_decay=0.0, momentum=0.0, betas=(0.9, 0.999), eps=1e-8,
+                 fused_eval=None):
+        """fused_eval (None: leave the model's switch): the model's eval-mode forwards (validation, panels) run the
+        fused eval forward; the train steps ignore it.
+        optimizer / schedule / ema_decay are the declared recipe (off by default: the reference's Adam at a
         constant rate).  schedule: None, a callable step -> lr, or a dict of lr_at() keywords plus num_epochs
         and steps_per_epoch (the per-epoch schedule of build/train); it is applied before every step."""
         self.model, self.loss_fn = model, loss_fn
+        _set_fused_eval(model, fused_eval)
         if optimizer == "adam" and ema_decay == 0.0 and momentum == 0.0 and tuple(betas) == (0.9, 0.999) and eps == 1e-8:
             self.optimizer = Adam(model, lr=lr, weight_decay=weight_decay)
         else:

@@ -189,6 +189,16 @@ cad_status cad_unet_set_tensor(cad_unet* h, int kind, int idx, const float* host
 cad_status cad_unet_get_tensor(const cad_unet* h, int kind, int idx, float* host, int64_t numel);
 cad_status cad_unet_get_grad(const cad_unet* h, int idx, float* host, int64_t numel);
 cad_status cad_unet_train(cad_unet* h, int train); /* 1 = train(), 0 = eval() */
+/* Fused eval forward (off by default): with on != 0 every eval-mode forward applies each block's
+ * BatchNorm + ReLU (+ FiLM) in its 3 x 3 convolutions' GEMM epilogues instead of a second pass over the pre-BN
+ * output, which is then never written ("enc<l>.y1|y2" debug buffers go stale).  Train-mode forwards ignore the
+ * switch.  fp32 engines: the same bits as the two-pass forward; bf16 engine: the activation is rounded to bf16
+ * once instead of twice.  The convolution feeding a fused level-0 head stays two-pass.
+ * cad_unet_fused_eval_convs: of the last forward's `total` 3 x 3 convolutions, `fused` ran the fused epilogue
+ * (either pointer may be NULL).  The ResNet-50 and geometry-aware handles have no such switch. */
+cad_status cad_unet_set_fused_eval(cad_unet* h, int on);
+int cad_unet_get_fused_eval(const cad_unet* h); /* 0 for a NULL handle */
+cad_status cad_unet_fused_eval_convs(const cad_unet* h, int* fused, int* total);
 /* flat parameter / gradient slabs (internal packed layout; n = elements incl. alignment padding) */
 cad_status cad_unet_flat(cad_unet* h, float** params, float** grads, int64_t* n);
 /* switch the flat slabs to caller-owned device memory of cad_unet_flat()'s n floats each (e.g.
@@ -815,6 +825,21 @@ cad_status cad_op_conv3x3_fwd_bf16(const void* x, int64_t ldx, int xcoff, int ci
                                    void* stream);
 cad_status cad_op_conv3x3_dgrad_bf16(const void* dz, int64_t lddz, int cout, const float* w_ohwi, int cin, void* dx,
                                      int64_t lddx, int dx_bf16, int B, int H, int W, void* stream);
+/* The fused eval forward's convolutions (cad_unet_set_fused_eval): cad_op_conv3x3_fwd / _fwd_bf16 with the
+ * block's eval-mode BatchNorm + ReLU and, with gam / bet, its FiLM modulation applied to the accumulator in the
+ * GEMM epilogue (EpiStoreAct), so the pre-BN output never reaches memory:
+ *   y[p][n] = max(fma(conv[p][n], scale[n], shift[n]), 0)                       gam == bet == NULL
+ *   y[p][n] = gam[b][n] * max(conv[p][n] * scale[n] + shift[n], 0) + bet[b][n]   b = p / (H W)
+ * scale / shift: cout floats; gam / bet: B x cout floats, both or neither.  H * W must be a multiple of 4.
+ * y_bf16: y holds bf16 rows (the activation rounded once, to nearest even) — the pre-split entry only; the
+ * fp32-operand entry stores fp32 and rejects y_bf16 != 0.  On CAD_GEMM_F32 the fp32 entry runs the same
+ * epilogue on the f32 im2col kernel. */
+cad_status cad_op_conv3x3_fwd_act(const float* x, int64_t ldx, int xcoff, int cin, const float* w_ohwi, int cout,
+                                  const float* scale, const float* shift, const float* gam, const float* bet, void* y,
+                                  int64_t ldy, int ycoff, int y_bf16, int B, int H, int W, void* stream);
+cad_status cad_op_conv3x3_fwd_act_bf16(const void* x, int64_t ldx, int xcoff, int cin, const float* w_ohwi, int cout,
+                                       const float* scale, const float* shift, const float* gam, const float* bet,
+                                       void* y, int64_t ldy, int ycoff, int y_bf16, int B, int H, int W, void* stream);
 cad_status cad_op_convT_fwd(const float* x, int cin, const float* w_iqo, const float* bias, int cout,
                             float* y, int64_t ldy, int ycoff, int B, int H, int W, void* stream);
 /* the bf16 engine's ConvTranspose2d(k2, s2) forward (baseline_unet.h:91 `up`) on a pre-split bf16 NHWC

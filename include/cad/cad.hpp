@@ -134,6 +134,14 @@ public:
     }
     void eval() { train(false); }
     bool is_training() const { return training_; }   // Module::is_training(): train mode after construction
+    // Fused eval forward (cad_unet_set_fused_eval; off by default): eval-mode forwards apply BatchNorm + ReLU
+    // (+ FiLM) in the convolutions' epilogues.  Train-mode forwards ignore it.
+    void fused_eval(bool on = true) { cad::check(cad_unet_set_fused_eval(h_, on ? 1 : 0), "fused_eval"); }
+    bool is_fused_eval() const { return cad_unet_get_fused_eval(h_) != 0; }
+    // of the last forward's `total` 3 x 3 convolutions, `fused` ran the fused epilogue
+    void fused_eval_convs(int* fused, int* total) const {
+        cad::check(cad_unet_fused_eval_convs(h_, fused, total), "fused_eval_convs");
+    }
 
     std::vector<NamedTensor> named_parameters() const { return fetch(0); }
     std::vector<NamedTensor> named_buffers() const { return fetch(1); }

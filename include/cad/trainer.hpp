@@ -621,6 +621,9 @@ public:
         bool save_best_only = false;         // no periodic checkpoints (best_model.* and final_model.* only)
         int keep_last_n_checkpoints = 0;     // newest epoch checkpoints kept; 0 keeps all
         float ema_decay = 0.f;               // > 0: exponential moving average of the weights (U-Net family)
+        // Independent of the recipe: the model's eval-mode forwards (validation, the prediction panels) run the
+        // fused eval forward (BaselineUNetImpl::fused_eval; the train steps ignore it).  U-Net family only
+        bool fused_eval = false;
     };
 
     // ---- the declared recipe's pieces shared with GeometryTrainer ----
@@ -706,6 +709,7 @@ public:
         world_ = comm_ ? comm_->size() : 1;
         lr_ = config_.learning_rate;
         checkRecipe(config_, comm_ != nullptr);
+        if (config_.fused_eval) model_->fused_eval(true);
         if (config_.recipe_declared) {
             recipe_ = std::make_shared<optim::Optimizer>(*model_, optimOptions(config_));
             progress_.best_metric = config_.metric_lower_is_better ? INFINITY : -INFINITY;
@@ -1095,6 +1099,9 @@ public:
         if (config_.recipe_declared && config_.ema_decay != 0.f)
             throw std::runtime_error("ema: the weight average is built for the U-Net family only; turn ema off for "
                                      "the geometry-aware networks");
+        if (config_.fused_eval)
+            throw std::runtime_error("fused_eval: the fused eval forward is built for the U-Net family only; turn it off "
+                                     "for the geometry-aware networks");
         lr_ = config_.learning_rate;
         progress_.best_metric = config_.metric_lower_is_better ? INFINITY : -INFINITY;
         std::filesystem::create_directories(config_.checkpoint_dir);
