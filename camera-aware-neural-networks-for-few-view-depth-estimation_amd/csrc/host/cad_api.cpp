@@ -232,7 +232,7 @@ struct cad_unet {
     // was not written, the backward rebuilds the head's input gradient per row
     bool head_fused = false;
     // cad_unet_set_fused_eval: eval-mode forwards run BatchNorm + ReLU (+ FiLM) in the convolutions' epilogues
-    // (conv3x3_fwd_act; train mode ignores it).  fe_fused of fe_total 3 x 3 convolutions of the last forward did
+    // (conv3x3_fwd with ActCoeffs; train mode ignores it).  fe_fused of fe_total 3 x 3 convolutions of the last forward did
     bool fused_eval = false;
     int fe_fused = 0, fe_total = 0;
     // backward
@@ -717,10 +717,9 @@ void double_conv_fwd(cad_unet* h, DoubleConv& dc, const float* in, int64_t ldin,
     if (fuse && ps1 == ps) {
         bn(dc.b1, dc.c1.cin, ps1);
         if (ps1)
-            cad::conv3x3_fwd_ps_act(in_s, dc.c1.cin, sv(dc.c1.ws, 9 * dc.c1.cin), C, dc.a1s, C, 0, B, Hh, Ww, act1, st, true);
+            cad::conv3x3_fwd_ps(in_s, dc.c1.cin, sv(dc.c1.ws, 9 * dc.c1.cin), C, dc.a1s, C, 0, B, Hh, Ww, act1, st, true);
         else
-            cad::conv3x3_fwd_act(in, ldin, 0, dc.c1.cin, h->P(dc.c1.pidx), C, dc.a1, C, 0, B, Hh, Ww, act1, st,
-                                 fwd_wtwin(dc.c1));
+            cad::conv3x3_fwd(in, ldin, 0, dc.c1.cin, h->P(dc.c1.pidx), C, dc.a1, C, 0, B, Hh, Ww, act1, st, fwd_wtwin(dc.c1));
         ++h->fe_fused;
     } else {
         if (ps1) {
@@ -749,12 +748,11 @@ void double_conv_fwd(cad_unet* h, DoubleConv& dc, const float* in, int64_t ldin,
             const cad::ActCoeffs act2{dc.b2.scale, dc.b2.shift, nullptr, nullptr};
             bn(dc.b2, C, ps);
             if (ps)
-                cad::conv3x3_fwd_ps_act(sv(dc.a1s, C), C, sv(dc.c2.ws, 9 * C), C,
-                                        twin ? const_cast<void*>(out_s.p) : static_cast<void*>(out),
-                                        twin ? out_s.ld : ldo, twin ? out_s.coff : ocoff, B, Hh, Ww, act2, st, twin);
+                cad::conv3x3_fwd_ps(sv(dc.a1s, C), C, sv(dc.c2.ws, 9 * C), C,
+                                    twin ? const_cast<void*>(out_s.p) : static_cast<void*>(out),
+                                    twin ? out_s.ld : ldo, twin ? out_s.coff : ocoff, B, Hh, Ww, act2, st, twin);
             else
-                cad::conv3x3_fwd_act(dc.a1, C, 0, C, h->P(dc.c2.pidx), C, out, ldo, ocoff, B, Hh, Ww, act2, st,
-                                     fwd_wtwin(dc.c2));
+                cad::conv3x3_fwd(dc.a1, C, 0, C, h->P(dc.c2.pidx), C, out, ldo, ocoff, B, Hh, Ww, act2, st, fwd_wtwin(dc.c2));
             ++h->fe_fused;
             return;
         }
@@ -3015,23 +3013,54 @@ cad_status cad_aug_sampler_draw(cad_aug_sampler* s, int height, int width, cad_s
     });
 }
 
+}  // extern "C"
+
 // ---------------- operator-level entry points ----------------
+namespace {
+// stream-ordered scratch of one entry point: freed on the stream when the call returns or throws
+struct OpScratch {
+    hipStream_t st;
+    std::vector<void*> held;
+    explicit OpScratch(hipStream_t s) : st(s) {}
+    template <class T>
+    T* take(size_t n) {
+        void* p = nullptr;
+        HIPCHK(hipMallocAsync(&p, sizeof(T) * std::max<size_t>(n, 4), st));
+        held.push_back(p);
+        return static_cast<T*>(p);
+    }
+    ~OpScratch() {
+        for (void* p : held) (void)hipFreeAsync(p, st);
+    }
+};
+// the S3 window kernels' weight twin of a conv3x3 (kind: WPREP_WTWIN_FWD, or _DGRAD with the GEMM's cin / n the
+// convolution's cout / cin), built for this call when that path is on; nullptr otherwise
+void* op_wtwin(OpScratch& scr, int kind, const float* w, int cout, int cin, int gemm_cin, int W, int gemm_n) {
+    const int bn = cad::conv3x3_wtwin_on() ? cad::conv3x3_wtwin_bn(gemm_cin, W, gemm_n) : 0;
+    if (!bn) return nullptr;
+    void* twin = scr.take<char>((size_t)cad::conv3x3_wtwin_bytes(gemm_cin, gemm_n));
+    cad::WPrepList L{};
+    wprep_twin_add(L, kind, w, twin, cout, cin, bn);
+    cad::weight_prep(L, scr.st);
+    return twin;
+}
+// the bf16 twin of `rows` dense fp32 weight rows of `cols`
+cad::Split op_wsplit(OpScratch& scr, const float* w, int rows, int cols) {
+    void* ws = scr.take<uint16_t>((size_t)rows * cols);
+    cad::split_rows(w, cols, 0, cols, rows, ws, cols, 0, scr.st);
+    return cad::Split{ws, cols, 0};
+}
+}  // namespace
+
+extern "C" {
 cad_status cad_op_conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y,
                               int64_t ldy, int ycoff, int B, int H, int W, void* stream) {
     return guard([&] {
         require(cin % 4 == 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && xcoff % 4 == 0 && ycoff % 4 == 0,
                 "channels / strides must be multiples of 4");
-        // the S3 window kernels' weight twin, built for this call when that path is on
-        void* twin = nullptr;
-        const int bn = cad::conv3x3_wtwin_on() ? cad::conv3x3_wtwin_bn(cin, W, cout) : 0;
-        if (bn) {
-            HIPCHK(hipMallocAsync(&twin, (size_t)cad::conv3x3_wtwin_bytes(cin, cout), S(stream)));
-            cad::WPrepList L{};
-            wprep_twin_add(L, cad::WPREP_WTWIN_FWD, w, twin, cout, cin, bn);
-            cad::weight_prep(L, S(stream));
-        }
+        OpScratch scr(S(stream));
+        void* twin = op_wtwin(scr, cad::WPREP_WTWIN_FWD, w, cout, cin, cin, W, cout);
         cad::conv3x3_fwd(x, ldx, xcoff, cin, w, cout, y, ldy, ycoff, B, H, W, nullptr, S(stream), twin);
-        if (twin) HIPCHK(hipFreeAsync(twin, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -3054,17 +3083,10 @@ cad_status cad_op_conv3x3_fwd_act(const float* x, int64_t ldx, int xcoff, int ci
         require(cin > 0 && cout > 0 && cin % 4 == 0 && cout % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && xcoff % 4 == 0 &&
                     ycoff % 4 == 0 && xcoff >= 0 && ycoff >= 0 && ldx >= xcoff + cin && ldy >= ycoff + cout,
                 "channels / strides must be multiples of 4 and the views must fit their rows");
-        void* twin = nullptr;
-        const int bn = cad::conv3x3_wtwin_on() ? cad::conv3x3_wtwin_bn(cin, W, cout) : 0;
-        if (bn) {
-            HIPCHK(hipMallocAsync(&twin, (size_t)cad::conv3x3_wtwin_bytes(cin, cout), S(stream)));
-            cad::WPrepList L{};
-            wprep_twin_add(L, cad::WPREP_WTWIN_FWD, w, twin, cout, cin, bn);
-            cad::weight_prep(L, S(stream));
-        }
-        cad::conv3x3_fwd_act(x, ldx, xcoff, cin, w, cout, static_cast<float*>(y), ldy, ycoff, B, H, W,
-                             cad::ActCoeffs{scale, shift, gam, bet}, S(stream), twin);
-        if (twin) HIPCHK(hipFreeAsync(twin, S(stream)));
+        OpScratch scr(S(stream));
+        void* twin = op_wtwin(scr, cad::WPREP_WTWIN_FWD, w, cout, cin, cin, W, cout);
+        cad::conv3x3_fwd(x, ldx, xcoff, cin, w, cout, static_cast<float*>(y), ldy, ycoff, B, H, W,
+                         cad::ActCoeffs{scale, shift, gam, bet}, S(stream), twin);
         HIPCHK(hipGetLastError());
     });
 }
@@ -3078,12 +3100,9 @@ cad_status cad_op_conv3x3_fwd_act_bf16(const void* x, int64_t ldx, int xcoff, in
                     ldx >= xcoff + cin && ldy >= ycoff + cout && cout % 4 == 0,
                 "bad arguments (bf16 rows: ldx, xcoff, cin multiples of 8; the views must fit their rows)");
         require(cad::gemm_engine() == 2, "the pre-split convolution runs on the bf16 engine (CAD_GEMM_BF16)");
-        void* ws = nullptr;
-        HIPCHK(hipMallocAsync(&ws, sizeof(uint16_t) * (size_t)cout * 9 * cin, S(stream)));
-        cad::split_rows(w, 9 * cin, 0, 9 * cin, cout, ws, 9 * cin, 0, S(stream));
-        cad::conv3x3_fwd_ps_act(cad::Split{x, ldx, xcoff}, cin, cad::Split{ws, 9 * cin, 0}, cout, y, ldy, ycoff, B, H, W,
-                                cad::ActCoeffs{scale, shift, gam, bet}, S(stream), y_bf16 != 0);
-        HIPCHK(hipFreeAsync(ws, S(stream)));
+        OpScratch scr(S(stream));
+        cad::conv3x3_fwd_ps(cad::Split{x, ldx, xcoff}, cin, op_wsplit(scr, w, cout, 9 * cin), cout, y, ldy, ycoff, B, H, W,
+                            cad::ActCoeffs{scale, shift, gam, bet}, S(stream), y_bf16 != 0);
         HIPCHK(hipGetLastError());
     });
 }
@@ -3091,20 +3110,11 @@ cad_status cad_op_conv3x3_dgrad(const float* dz, int cout, const float* w, int c
                                 int H, int W, void* stream) {
     return guard([&] {
         require(cin % 4 == 0 && cout % 4 == 0, "channels must be multiples of 4");
-        float* wd = nullptr;
-        HIPCHK(hipMallocAsync((void**)&wd, sizeof(float) * (size_t)cout * 9 * cin, S(stream)));
+        OpScratch scr(S(stream));
+        float* wd = scr.take<float>((size_t)cout * 9 * cin);
         cad::repack_conv_dgrad(w, wd, cout, cin, S(stream));
-        void* twin = nullptr;
-        const int bn = cad::conv3x3_wtwin_on() ? cad::conv3x3_wtwin_bn(cout, W, cin) : 0;
-        if (bn) {
-            HIPCHK(hipMallocAsync(&twin, (size_t)cad::conv3x3_wtwin_bytes(cout, cin), S(stream)));
-            cad::WPrepList L{};
-            wprep_twin_add(L, cad::WPREP_WTWIN_DGRAD, w, twin, cout, cin, bn);
-            cad::weight_prep(L, S(stream));
-        }
+        void* twin = op_wtwin(scr, cad::WPREP_WTWIN_DGRAD, w, cout, cin, cout, W, cin);
         cad::conv3x3_dgrad(dz, cout, wd, cin, dx, lddx, B, H, W, S(stream), twin);
-        if (twin) HIPCHK(hipFreeAsync(twin, S(stream)));
-        HIPCHK(hipFreeAsync(wd, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -3113,10 +3123,9 @@ cad_status cad_op_conv3x3_wgrad(const float* dz, int cout, const float* x, int64
     return guard([&] {
         require(cin % 4 == 0 && cout % 4 == 0, "channels must be multiples of 4");
         const int64_t cap = cad::wgrad_slab_floats(cout, 9 * cin, B * H * W);
-        float* slab = nullptr;
-        HIPCHK(hipMallocAsync((void**)&slab, sizeof(float) * (size_t)std::max<int64_t>(cap, 4), S(stream)));
+        OpScratch scr(S(stream));
+        float* slab = scr.take<float>((size_t)cap);
         cad::conv3x3_wgrad(dz, cout, x, ldx, xcoff, cin, dw, B, H, W, slab, cap, S(stream));
-        HIPCHK(hipFreeAsync(slab, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -3125,11 +3134,10 @@ cad_status cad_op_conv3x3_wgrad_bf16(const void* dz, int64_t lddz, int cout, con
     return guard([&] {
         require(cad::gemm_engine() == 2, "the pre-split weight gradient runs on the bf16 engine (CAD_GEMM_BF16)");
         const int64_t cap = cad::wgrad_slab_floats(cout, 9 * cin, B * H * W);
-        float* slab = nullptr;
-        HIPCHK(hipMallocAsync((void**)&slab, sizeof(float) * (size_t)std::max<int64_t>(cap, 4), S(stream)));
+        OpScratch scr(S(stream));
+        float* slab = scr.take<float>((size_t)cap);
         cad::conv3x3_wgrad_ps(cad::Split{dz, lddz, 0}, cout, cad::Split{x, ldx, xcoff}, cin, dw, B, H, W, slab, cap,
                               S(stream));
-        HIPCHK(hipFreeAsync(slab, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -3139,18 +3147,14 @@ cad_status cad_op_conv3x3_fwd_bf16(const void* x, int64_t ldx, int xcoff, int ci
         require(cad::gemm_engine() == 2, "the pre-split convolution runs on the bf16 engine (CAD_GEMM_BF16)");
         require(x && w && y && cin % 8 == 0 && xcoff % 8 == 0 && ldx % 8 == 0 && B > 0 && H > 0 && W > 0,
                 "bad arguments (bf16 rows: ldx, xcoff, cin multiples of 8)");
-        void* ws = nullptr;
+        OpScratch scr(S(stream));
+        const cad::Split ws = op_wsplit(scr, w, cout, 9 * cin);
         float* stats = nullptr;
-        HIPCHK(hipMallocAsync(&ws, sizeof(uint16_t) * (size_t)cout * 9 * cin, S(stream)));
-        cad::split_rows(w, 9 * cin, 0, 9 * cin, cout, ws, 9 * cin, 0, S(stream));
         if (with_stats) {
             const int rows = cad::conv3x3_stats_rows(cin, B, H, W, cout, true);
-            HIPCHK(hipMallocAsync((void**)&stats, sizeof(float) * ((size_t)rows * (2 * cout + 1) + 4), S(stream)));
+            stats = scr.take<float>((size_t)rows * (2 * cout + 1) + 4);
         }
-        cad::conv3x3_fwd_ps(cad::Split{x, ldx, xcoff}, cin, cad::Split{ws, 9 * cin, 0}, cout, static_cast<float*>(y), ldy,
-                            ycoff, B, H, W, stats, S(stream), y_bf16 != 0);
-        if (stats) HIPCHK(hipFreeAsync(stats, S(stream)));
-        HIPCHK(hipFreeAsync(ws, S(stream)));
+        cad::conv3x3_fwd_ps(cad::Split{x, ldx, xcoff}, cin, ws, cout, y, ldy, ycoff, B, H, W, stats, S(stream), y_bf16 != 0);
         HIPCHK(hipGetLastError());
     });
 }
@@ -3160,16 +3164,11 @@ cad_status cad_op_conv3x3_dgrad_bf16(const void* dz, int64_t lddz, int cout, con
         require(cad::gemm_engine() == 2, "the pre-split convolution runs on the bf16 engine (CAD_GEMM_BF16)");
         require(dz && w && dx && cout % 8 == 0 && cin % 8 == 0 && lddz % 8 == 0 && B > 0 && H > 0 && W > 0,
                 "bad arguments (bf16 rows: lddz, cout, cin multiples of 8)");
-        float* wd = nullptr;
-        void* wds = nullptr;
-        HIPCHK(hipMallocAsync((void**)&wd, sizeof(float) * (size_t)cout * 9 * cin, S(stream)));
-        HIPCHK(hipMallocAsync(&wds, sizeof(uint16_t) * (size_t)cout * 9 * cin, S(stream)));
+        OpScratch scr(S(stream));
+        float* wd = scr.take<float>((size_t)cout * 9 * cin);
         cad::repack_conv_dgrad(w, wd, cout, cin, S(stream));
-        cad::split_rows(wd, 9 * cout, 0, 9 * cout, cin, wds, 9 * cout, 0, S(stream));
-        cad::conv3x3_dgrad_ps(cad::Split{dz, lddz, 0}, cout, cad::Split{wds, 9 * cout, 0}, cin, static_cast<float*>(dx),
+        cad::conv3x3_dgrad_ps(cad::Split{dz, lddz, 0}, cout, op_wsplit(scr, wd, cin, 9 * cout), cin, static_cast<float*>(dx),
                               lddx, B, H, W, S(stream), dx_bf16 != 0);
-        HIPCHK(hipFreeAsync(wds, S(stream)));
-        HIPCHK(hipFreeAsync(wd, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -3209,11 +3208,10 @@ cad_status cad_op_convT_fwd(const float* x, int cin, const float* w, const float
                             int64_t ldy, int ycoff, int B, int H, int W, void* stream) {
     return guard([&] {
         require(cin % 4 == 0 && cout % 4 == 0, "channels must be multiples of 4");
-        float* wf = nullptr;
-        HIPCHK(hipMallocAsync((void**)&wf, sizeof(float) * (size_t)cout * 4 * cin, S(stream)));
+        OpScratch scr(S(stream));
+        float* wf = scr.take<float>((size_t)cout * 4 * cin);
         cad::repack_convT_fwd(w, wf, cin, cout, S(stream));
         cad::convT_fwd(x, cin, cin, wf, bias, cout, y, ldy, ycoff, B, H, W, S(stream));
-        HIPCHK(hipFreeAsync(wf, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -3224,16 +3222,11 @@ cad_status cad_op_convT_fwd_bf16(const void* x, int64_t ldx, int xcoff, int cin,
         require(x && w && bias && y && cin % 8 == 0 && cout % 8 == 0 && xcoff % 8 == 0 && ldx % 8 == 0 &&
                     ldy % 8 == 0 && ycoff % 8 == 0 && B > 0 && H > 0 && W > 0,
                 "bad arguments (bf16 rows: ldx, xcoff, ldy, ycoff, cin, cout multiples of 8)");
-        float* wf = nullptr;
-        void* wfs = nullptr;
-        HIPCHK(hipMallocAsync((void**)&wf, sizeof(float) * (size_t)cout * 4 * cin, S(stream)));
-        HIPCHK(hipMallocAsync(&wfs, sizeof(uint16_t) * (size_t)cout * 4 * cin, S(stream)));
+        OpScratch scr(S(stream));
+        float* wf = scr.take<float>((size_t)cout * 4 * cin);
         cad::repack_convT_fwd(w, wf, cin, cout, S(stream));
-        cad::split_rows(wf, cin, 0, cin, 4 * cout, wfs, cin, 0, S(stream));
-        cad::convT_fwd_ps(cad::Split{x, ldx, xcoff}, cin, cad::Split{wfs, cin, 0}, bias, cout, static_cast<float*>(y),
-                          ldy, ycoff, B, H, W, S(stream), true);
-        HIPCHK(hipFreeAsync(wfs, S(stream)));
-        HIPCHK(hipFreeAsync(wf, S(stream)));
+        cad::convT_fwd_ps(cad::Split{x, ldx, xcoff}, cin, op_wsplit(scr, wf, 4 * cout, cin), bias, cout,
+                          static_cast<float*>(y), ldy, ycoff, B, H, W, S(stream), true);
         HIPCHK(hipGetLastError());
     });
 }
@@ -3250,10 +3243,9 @@ cad_status cad_op_convT_wgrad(const float* x, int cin, const float* g, int64_t l
     return guard([&] {
         require(cin % 4 == 0 && cout % 4 == 0, "channels must be multiples of 4");
         const int64_t cap = cad::wgrad_slab_floats(cin, 4 * cout, B * H * W);
-        float* slab = nullptr;
-        HIPCHK(hipMallocAsync((void**)&slab, sizeof(float) * (size_t)std::max<int64_t>(cap, 4), S(stream)));
+        OpScratch scr(S(stream));
+        float* slab = scr.take<float>((size_t)cap);
         cad::convT_wgrad(x, cin, g, ldg, gcoff, cout, dw, B, H, W, slab, cap, S(stream));
-        HIPCHK(hipFreeAsync(slab, S(stream)));
         HIPCHK(hipGetLastError());
     });
 }
@@ -3270,22 +3262,6 @@ cad_status cad_op_maxpool_fwd(const float* x, int64_t ldx, int C, int B, int H, 
 
 // ---------------- config-5 operator entry points (resunet.cpp's launchers, one per call) ----------------
 namespace {
-// stream-ordered scratch of one entry point: freed on the stream when the call returns or throws
-struct OpScratch {
-    hipStream_t st;
-    std::vector<void*> held;
-    explicit OpScratch(hipStream_t s) : st(s) {}
-    template <class T>
-    T* take(size_t n) {
-        void* p = nullptr;
-        HIPCHK(hipMallocAsync(&p, sizeof(T) * std::max<size_t>(n, 4), st));
-        held.push_back(p);
-        return static_cast<T*>(p);
-    }
-    ~OpScratch() {
-        for (void* p : held) (void)hipFreeAsync(p, st);
-    }
-};
 bool conv_geom_ok(int B, int H, int W, int KH, int KW, int S, int P) {
     return B > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && S > 0 && P >= 0 && H + 2 * P >= KH && W + 2 * P >= KW;
 }

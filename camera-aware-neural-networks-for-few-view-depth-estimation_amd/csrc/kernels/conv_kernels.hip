@@ -359,108 +359,68 @@ constexpr int kS3KB = 16;
 constexpr int kB1KB = 32;
 int ps_kb(bool conv_fwd_kind, Cfg c) { return conv_fwd_kind && c == C22 ? 64 : 32; }
 
-template <template <int, int, int> class KT, int WM, int WN, int KB>
-void launch_one(const GemmArgs& a, int splits, hipStream_t st) {
-    using K = KT<WM, WN, KB>;
-    const dim3 grid(cdiv(a.M, 64 * WM), cdiv(a.N, 64 * WN), splits);
-    if (prof_enabled()) {
-        char name[160];
-        snprintf(name, sizeof(name), K::fmt, WM, WN, KB);
-        prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-        hipLaunchKernelGGL(K::fn(), grid, dim3(256), 0, st, a);
-        prof_pop(st);
-    } else {
-        hipLaunchKernelGGL(K::fn(), grid, dim3(256), 0, st, a);
-    }
+// Kernel families: one tag per kernel template <WM, WN, KB[, Epi]>, templated on the epilogue (void: a
+// family whose epilogue is fixed).  `base` and Epi::name make the profiler name (KName, kernels.hpp).
+// The kernel pointer sits behind fn(): a specialization is instantiated only where it is launched.
+#define CAD_KFAM(TAG, KERN)                                             \
+    template <class Epi = void> struct TAG {                            \
+        static constexpr const char* base = #KERN;                      \
+        static constexpr const char* epi() {                            \
+            if constexpr (std::is_void_v<Epi>) return nullptr;          \
+            else return Epi::name;                                      \
+        }                                                               \
+        template <int WM, int WN, int KB> static auto fn() {            \
+            if constexpr (std::is_void_v<Epi>) return KERN<WM, WN, KB>; \
+            else return KERN<WM, WN, KB, Epi>;                          \
+        }                                                               \
+    };
+// per engine: ...F (f32), ...3 (S3), ...B (B1, in-loader split), ...P1 (B1 on the pre-split twins)
+#define CAD_KFAMS(SUF, T)                                                                       \
+    CAD_KFAM(KConvFwd##T, k_conv3x3_fwd##SUF) CAD_KFAM(KConvWgrad##T, k_conv3x3_wgrad##SUF)     \
+    CAD_KFAM(KConvTFwd##T, k_convT_fwd##SUF) CAD_KFAM(KConvTDgrad##T, k_convT_dgrad##SUF)       \
+    CAD_KFAM(KConvTWgrad##T, k_convT_wgrad##SUF)
+CAD_KFAMS(, F)
+CAD_KFAMS(_s3, 3)
+CAD_KFAMS(_bf16, B)
+CAD_KFAMS(_bf16p, P1)
+CAD_KFAM(KConvTFwdP1T, k_convT_fwd_bf16pt)
+CAD_KFAM(KConvTDgradP1B, k_convT_dgrad_bf16pb)
+CAD_KFAM(KDenseP1, k_dense_bf16p)
+CAD_KFAM(KDenseWgradP1, k_dense_wgrad_bf16p)
+#undef CAD_KFAMS
+#undef CAD_KFAM
+
+template <class K, int WM, int WN, int KB>
+void launch_tile(const GemmArgs& a, int splits, hipStream_t st) {
+    launch_gemm(K::template fn<WM, WN, KB>(), KName{K::base, 3, {WM, WN, KB}, K::epi()},
+                dim3(cdiv(a.M, 64 * WM), cdiv(a.N, 64 * WN), splits), a, st);
 }
-template <template <int, int, int> class KT, int KB>
+template <class K, int KB>
 void launch_cfg(Cfg c, const GemmArgs& a, int splits, hipStream_t st) {
     switch (c) {
-        case C41: launch_one<KT, 4, 1, KB>(a, splits, st); break;
-        case C22: launch_one<KT, 2, 2, KB>(a, splits, st); break;
-        case C14: launch_one<KT, 1, 4, KB>(a, splits, st); break;
+        case C41: launch_tile<K, 4, 1, KB>(a, splits, st); break;
+        case C22: launch_tile<K, 2, 2, KB>(a, splits, st); break;
+        case C14: launch_tile<K, 1, 4, KB>(a, splits, st); break;
     }
 }
 // stage depth kb among the ones a kernel family is built for (KBs)
-template <template <int, int, int> class KT, int... KBs>
+template <class K, int... KBs>
 void launch_kb(Cfg c, int kb, const GemmArgs& a, int splits, hipStream_t st) {
-    const bool done = ((kb == KBs ? (launch_cfg<KT, KBs>(c, a, splits, st), true) : false) || ...);
+    const bool done = ((kb == KBs ? (launch_cfg<K, KBs>(c, a, splits, st), true) : false) || ...);
     if (!done) throw std::runtime_error("GEMM stage depth not built for this kernel family");
 }
-// fmt = the symbol as rocprofv3 demangles it
-// (kernel pointers behind functions: a specialization is instantiated only when launched)
-#define CAD_KT(NAME, EXPR, FMT)                                                  \
-    template <int WM, int WN, int KB> struct NAME {                              \
-        static auto fn() { return EXPR; }                                        \
-        static constexpr const char* fmt = FMT;                                  \
-    };
-CAD_KT(KConvFwd, (k_conv3x3_fwd<WM, WN, KB, EpiStore>), "void cad::k_conv3x3_fwd<%d, %d, %d, cad::EpiStore>(cad::GemmArgs)")
-CAD_KT(KConvFwdS, (k_conv3x3_fwd<WM, WN, KB, EpiStoreStats>),
-       "void cad::k_conv3x3_fwd<%d, %d, %d, cad::EpiStoreStats>(cad::GemmArgs)")
-CAD_KT(KConvWgrad, (k_conv3x3_wgrad<WM, WN, KB>), "void cad::k_conv3x3_wgrad<%d, %d, %d>(cad::GemmArgs)")
-CAD_KT(KConvTFwd, (k_convT_fwd<WM, WN, KB>), "void cad::k_convT_fwd<%d, %d, %d>(cad::GemmArgs)")
-CAD_KT(KConvTDgrad, (k_convT_dgrad<WM, WN, KB>), "void cad::k_convT_dgrad<%d, %d, %d>(cad::GemmArgs)")
-CAD_KT(KConvTWgrad, (k_convT_wgrad<WM, WN, KB>), "void cad::k_convT_wgrad<%d, %d, %d>(cad::GemmArgs)")
-#define CAD_NP_KT(SUF, T)                                                                                  \
-    CAD_KT(KConvFwd##T, (k_conv3x3_fwd_##SUF<WM, WN, KB, EpiStore>),                                       \
-           "void cad::k_conv3x3_fwd_" #SUF "<%d, %d, %d, cad::EpiStore>(cad::GemmArgs)")                   \
-    CAD_KT(KConvFwdS##T, (k_conv3x3_fwd_##SUF<WM, WN, KB, EpiStoreStats>),                                 \
-           "void cad::k_conv3x3_fwd_" #SUF "<%d, %d, %d, cad::EpiStoreStats>(cad::GemmArgs)")              \
-    CAD_KT(KConvTFwd##T, (k_convT_fwd_##SUF<WM, WN, KB>), "void cad::k_convT_fwd_" #SUF "<%d, %d, %d>(cad::GemmArgs)") \
-    CAD_KT(KConvTDgrad##T, (k_convT_dgrad_##SUF<WM, WN, KB>),                                              \
-           "void cad::k_convT_dgrad_" #SUF "<%d, %d, %d>(cad::GemmArgs)")                                  \
-    CAD_KT(KConvWgrad##T, (k_conv3x3_wgrad_##SUF<WM, WN, KB>),                                             \
-           "void cad::k_conv3x3_wgrad_" #SUF "<%d, %d, %d>(cad::GemmArgs)")                                \
-    CAD_KT(KConvTWgrad##T, (k_convT_wgrad_##SUF<WM, WN, KB>),                                              \
-           "void cad::k_convT_wgrad_" #SUF "<%d, %d, %d>(cad::GemmArgs)")
-CAD_KT(KDenseP1, (k_dense_bf16p<WM, WN, KB, EpiStore>), "void cad::k_dense_bf16p<%d, %d, %d, cad::EpiStore>(cad::GemmArgs)")
-CAD_KT(KDenseSP1, (k_dense_bf16p<WM, WN, KB, EpiStoreStats>),
-       "void cad::k_dense_bf16p<%d, %d, %d, cad::EpiStoreStats>(cad::GemmArgs)")
-CAD_KT(KDenseP1B, (k_dense_bf16p<WM, WN, KB, EpiStoreB16>), "void cad::k_dense_bf16p<%d, %d, %d, cad::EpiStoreB16>(cad::GemmArgs)")
-CAD_KT(KDenseSP1B, (k_dense_bf16p<WM, WN, KB, EpiStoreStatsB16>),
-       "void cad::k_dense_bf16p<%d, %d, %d, cad::EpiStoreStatsB16>(cad::GemmArgs)")
-CAD_KT(KConvFwdP1B, (k_conv3x3_fwd_bf16p<WM, WN, KB, EpiStoreB16>),
-       "void cad::k_conv3x3_fwd_bf16p<%d, %d, %d, cad::EpiStoreB16>(cad::GemmArgs)")
-CAD_KT(KConvFwdSP1B, (k_conv3x3_fwd_bf16p<WM, WN, KB, EpiStoreStatsB16>),
-       "void cad::k_conv3x3_fwd_bf16p<%d, %d, %d, cad::EpiStoreStatsB16>(cad::GemmArgs)")
-CAD_KT(KDenseWgradP1, (k_dense_wgrad_bf16p<WM, WN, KB>), "void cad::k_dense_wgrad_bf16p<%d, %d, %d>(cad::GemmArgs)")
-CAD_KT(KConvTFwdP1T, (k_convT_fwd_bf16pt<WM, WN, KB>), "void cad::k_convT_fwd_bf16pt<%d, %d, %d>(cad::GemmArgs)")
-CAD_KT(KConvTDgradP1B, (k_convT_dgrad_bf16pb<WM, WN, KB>), "void cad::k_convT_dgrad_bf16pb<%d, %d, %d>(cad::GemmArgs)")
-CAD_KT(KDenseAddP1, (k_dense_bf16p<WM, WN, KB, EpiStoreAdd>), "void cad::k_dense_bf16p<%d, %d, %d, cad::EpiStoreAdd>(cad::GemmArgs)")
-// in-loader split engines: KConvFwd3 ... (S3), KConvFwdB ... (B1); pre-split B1: KConvFwdP1 ...
-CAD_NP_KT(s3, 3)
-CAD_NP_KT(bf16, B)
-CAD_NP_KT(bf16p, P1)
-#undef CAD_NP_KT
-// the im2col forwards with the eval-mode activation epilogue (EpiStoreAct<bf16 output, FiLM>): KConvFwdAct<F>
-// (f32), ...3 (S3), ...B (B1 in-loader), ...P1 (B1 pre-split; O = bf16 output)
-#define CAD_ACT_KT(NAME, KERN, OB, FI)                             \
-    CAD_KT(NAME, (KERN<WM, WN, KB, EpiStoreAct<OB, FI>>),          \
-           "void cad::" #KERN "<%d, %d, %d, cad::EpiStoreAct<" #OB ", " #FI ">>(cad::GemmArgs)")
-CAD_ACT_KT(KConvFwdAct, k_conv3x3_fwd, false, false)
-CAD_ACT_KT(KConvFwdActF, k_conv3x3_fwd, false, true)
-CAD_ACT_KT(KConvFwdAct3, k_conv3x3_fwd_s3, false, false)
-CAD_ACT_KT(KConvFwdActF3, k_conv3x3_fwd_s3, false, true)
-CAD_ACT_KT(KConvFwdActB, k_conv3x3_fwd_bf16, false, false)
-CAD_ACT_KT(KConvFwdActFB, k_conv3x3_fwd_bf16, false, true)
-CAD_ACT_KT(KConvFwdActP1, k_conv3x3_fwd_bf16p, false, false)
-CAD_ACT_KT(KConvFwdActFP1, k_conv3x3_fwd_bf16p, false, true)
-CAD_ACT_KT(KConvFwdActOP1, k_conv3x3_fwd_bf16p, true, false)
-CAD_ACT_KT(KConvFwdActFOP1, k_conv3x3_fwd_bf16p, true, true)
-#undef CAD_ACT_KT
-#undef CAD_KT
 
 // `splits` launches of one contraction on the current engine with in-loader operand conversion:
-// F = f32 kernel, T3 = S3, TB = B1; `fwd_kind` selects the deeper f32 stage of the conv3x3
+// F = f32 family, T3 = S3, TB = B1; `fwd_kind` selects the deeper f32 stage of the conv3x3
 // forward/dgrad.  a.kstages_per_split must be set.
-template <template <int, int, int> class F, template <int, int, int> class T3, template <int, int, int> class TB>
+template <class F, class T3, class TB>
 void launch_on_engine(Cfg c, int kb, const GemmArgs& a, int splits, hipStream_t st) {
     if (engine() == 1) launch_kb<T3, kS3KB>(c, kb, a, splits, st);
     else if (engine() == 2) launch_kb<TB, kB1KB>(c, kb, a, splits, st);
     else launch_kb<F, 16, 32>(c, kb, a, splits, st);
 }
 int engine_kb(bool fwd_kind, Cfg c) { return engine() == 1 ? kS3KB : engine() == 2 ? kB1KB : f32_kb(fwd_kind, c); }
-template <template <int, int, int> class F, template <int, int, int> class T3, template <int, int, int> class TB>
+template <class F, class T3, class TB>
 void launch_engine(Cfg c, bool fwd_kind, GemmArgs& a, hipStream_t st) {
     const int kb = engine_kb(fwd_kind, c);
     a.kstages_per_split = cdiv(a.K, kb);
@@ -494,84 +454,52 @@ WinPick pick_win_shape(int cin, int W, int N) {
 }
 WinPick pick_win(int cin, int W, int N) { return engine() == 1 ? pick_win_shape(cin, W, N) : WinPick{}; }
 int win_blocks(const WinPick& w, int B, int H, int W) { return B * cdiv(H, w.R) * (W / w.CW); }
-// the profiler's name of a plain-store or activation epilogue (EpiStoreAct<bf16 output, FiLM>)
-template <class Epi>
-const char* act_name() {
-    if constexpr (is_act<Epi>::value)
-        return Epi::BF16 ? (Epi::FILM ? "EpiStoreAct<true, true>" : "EpiStoreAct<true, false>")
-                         : (Epi::FILM ? "EpiStoreAct<false, true>" : "EpiStoreAct<false, false>");
-    else
-        return "EpiStore";
-}
 // PS = false: S3 window kernel (fp32 operands, in-loader split); true: B1 on the pre-split twins
 template <bool PS, int R, int CW, class Epi, bool BIG = false, bool N96 = false>
 void launch_win1(const GemmArgs& a, hipStream_t st) {
     constexpr int BN = N96 ? 96 : BIG ? (R * CW == 256 ? 128 : 64) : R * CW == 128 ? 128 : 64;
     if (a.N % BN) throw std::runtime_error("window conv: N not a multiple of the tile");
     const dim3 grid(win_blocks(WinPick{R, CW}, a.B, a.H, a.W), cdiv(a.N, BN));
-    void (*fn)(GemmArgs);
-    if constexpr (N96) fn = k_conv3x3_win_bf16p3<R, CW, Epi>;
-    else if constexpr (BIG) fn = k_conv3x3_win_bf16p4<R, CW, Epi, BN == 64>;
-    else if constexpr (PS) fn = k_conv3x3_win_bf16p<R, CW, Epi>;
-    else fn = a.wtwin ? (void (*)(GemmArgs))k_conv3x3_win_s3<R, CW, Epi, true> : (void (*)(GemmArgs))k_conv3x3_win_s3<R, CW, Epi>;
-    if (prof_enabled()) {
-        char name[160];
-        snprintf(name, sizeof(name), "void cad::k_conv3x3_win_%s<%d, %d, cad::%s%s%s>(cad::GemmArgs)",
-                 N96 ? "bf16p3" : BIG ? "bf16p4" : PS ? "bf16p" : "s3", R, CW,
-                 Epi::STATS ? "EpiStoreStats" : is_bnsums<Epi>::value ? "EpiStoreBnSums" : act_name<Epi>(),
-                 Epi::BF16 && !is_act<Epi>::value ? "B16" : "", !PS && !N96 && !BIG && a.wtwin ? ", true" : "");
-        prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
-        prof_pop(st);
+    KName name{"k_conv3x3_win_s3", 2, {R, CW}, Epi::name};
+    void (*fn)(GemmArgs) = nullptr;
+    if constexpr (N96) {
+        fn = k_conv3x3_win_bf16p3<R, CW, Epi>;
+        name.base = "k_conv3x3_win_bf16p3";
+    } else if constexpr (BIG) {
+        fn = k_conv3x3_win_bf16p4<R, CW, Epi, BN == 64>;
+        name.base = "k_conv3x3_win_bf16p4";
+    } else if constexpr (PS) {
+        fn = k_conv3x3_win_bf16p<R, CW, Epi>;
+        name.base = "k_conv3x3_win_bf16p";
+    } else if (a.wtwin) {
+        fn = k_conv3x3_win_s3<R, CW, Epi, true>;
+        name.tail = "true";
     } else {
-        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
+        fn = k_conv3x3_win_s3<R, CW, Epi>;
     }
+    launch_gemm(fn, name, grid, a, st);
+}
+// the block shapes (R, CW) a tile family is built for; the pick's CW selects one
+template <int R_, int CW_> struct Blk { static constexpr int R = R_, CW = CW_; };
+template <class... Bs> struct Blks {};
+using Blk128 = Blks<Blk<2, 64>, Blk<4, 32>, Blk<8, 16>, Blk<16, 8>>;                    // 128 pixels
+using Blk256 = Blks<Blk<2, 128>, Blk<4, 64>, Blk<8, 32>, Blk<16, 16>, Blk<32, 8>>;     // 256 pixels, B1 big tiles
+using Blk256N = Blks<Blk<2, 128>, Blk<4, 64>>;                                          // 256 pixels x 64 columns
+using Blk512 = Blks<Blk<4, 128>, Blk<8, 64>>;                                           // 512 pixels x 64 columns
+template <bool PS, class Epi, bool BIG = false, bool N96 = false, class... Bs>
+void launch_win_of(Blks<Bs...>, const WinPick& w, const GemmArgs& a, hipStream_t st) {
+    const bool done = ((w.CW == Bs::CW ? (launch_win1<PS, Bs::R, Bs::CW, Epi, BIG, N96>(a, st), true) : false) || ...);
+    if (!done) throw std::runtime_error("window conv: block shape not built");
 }
 template <class Epi, bool PS = false>
 void launch_win(const WinPick& w, const GemmArgs& a, hipStream_t st) {
     if constexpr (PS) {
-        if (w.n96) {   // 256 x 96
-            switch (w.CW) {
-                case 128: launch_win1<PS, 2, 128, Epi, true, true>(a, st); return;
-                case 64: launch_win1<PS, 4, 64, Epi, true, true>(a, st); return;
-                case 32: launch_win1<PS, 8, 32, Epi, true, true>(a, st); return;
-                case 16: launch_win1<PS, 16, 16, Epi, true, true>(a, st); return;
-                case 8: launch_win1<PS, 32, 8, Epi, true, true>(a, st); return;
-            }
-            throw std::runtime_error("window conv: block shape not built");
-        }
-        if (w.big && w.R * w.CW == 256) {
-            switch (w.CW) {
-                case 128: launch_win1<PS, 2, 128, Epi, true>(a, st); return;
-                case 64: launch_win1<PS, 4, 64, Epi, true>(a, st); return;
-                case 32: launch_win1<PS, 8, 32, Epi, true>(a, st); return;
-                case 16: launch_win1<PS, 16, 16, Epi, true>(a, st); return;
-                case 8: launch_win1<PS, 32, 8, Epi, true>(a, st); return;
-            }
-            throw std::runtime_error("window conv: block shape not built");
-        }
-        if (w.big) {   // 512 x 64
-            switch (w.CW) {
-                case 128: launch_win1<PS, 4, 128, Epi, true>(a, st); return;
-                case 64: launch_win1<PS, 8, 64, Epi, true>(a, st); return;
-            }
-            throw std::runtime_error("window conv: block shape not built");
-        }
+        if (w.n96) return launch_win_of<PS, Epi, true, true>(Blk256{}, w, a, st);   // 256 x 96
+        if (w.big && w.R * w.CW == 256) return launch_win_of<PS, Epi, true>(Blk256{}, w, a, st);
+        if (w.big) return launch_win_of<PS, Epi, true>(Blk512{}, w, a, st);   // 512 x 64
     }
-    if (w.R * w.CW == 128) {
-        switch (w.CW) {
-            case 64: launch_win1<PS, 2, 64, Epi>(a, st); return;
-            case 32: launch_win1<PS, 4, 32, Epi>(a, st); return;
-            case 16: launch_win1<PS, 8, 16, Epi>(a, st); return;
-            case 8: launch_win1<PS, 16, 8, Epi>(a, st); return;
-        }
-    } else {
-        switch (w.CW) {
-            case 128: launch_win1<PS, 2, 128, Epi>(a, st); return;
-            case 64: launch_win1<PS, 4, 64, Epi>(a, st); return;
-        }
-    }
-    throw std::runtime_error("window conv: block shape not built");
+    if (w.R * w.CW == 128) launch_win_of<PS, Epi>(Blk128{}, w, a, st);
+    else launch_win_of<PS, Epi>(Blk256N{}, w, a, st);
 }
 // B1 window kernel on the pre-split twins: 32-channel stages
 WinPick pick_win_ps(int cin, int W, int N, int acoff) {
@@ -648,9 +576,8 @@ int plan_splits(const GemmArgs& a, Cfg c, int kb, int64_t slab_cap_floats, int64
 constexpr int kSlabGroup = 24;
 void slab_reduce(float* slab, int nsplit, int64_t per, int zstep, float* dst, unsigned bx, unsigned by, hipStream_t st) {
     // profiled (0 FLOP) so a launch profile shows which reduction plan ran
-    if (prof_enabled()) prof_push("cad::k_slab_reduce(float*, int, long, int, float*, long)", 0.0, st);
-    hipLaunchKernelGGL(k_slab_reduce, dim3(bx, by), dim3(256), 0, st, slab, nsplit, per, zstep, dst, per);
-    if (prof_enabled()) prof_pop(st);
+    launch_prof(k_slab_reduce, "cad::k_slab_reduce(float*, int, long, int, float*, long)", 0.0, dim3(bx, by), st, slab,
+                nsplit, per, zstep, dst, per);
 }
 void finish_slabs(float* slab, int splits, int64_t per, float* dw, hipStream_t st) {
     const unsigned bx = (unsigned)cdiv(per / 4, 256);
@@ -792,14 +719,8 @@ bool wgrad_narrow_s3(const float* dz, int64_t ldz, const float* x, int64_t ldx, 
     if (s > 1 && (int64_t)s * per > slab_cap) return false;
     float* out = s == 1 ? dw : slab;
     const dim3 grid(s, cout / 64);
-    if (prof_enabled()) prof_push("cad::k_wgrad_narrow_s3", 2.0 * M * per, st);
-    if (9 * cin <= 32)
-        hipLaunchKernelGGL(k_wgrad_narrow_s3<1>, grid, dim3(256), 0, st, dz, ldz, x, ldx, xoff, cin, cout, B, H, W, ppw, out);
-    else if (9 * cin <= 64)
-        hipLaunchKernelGGL(k_wgrad_narrow_s3<2>, grid, dim3(256), 0, st, dz, ldz, x, ldx, xoff, cin, cout, B, H, W, ppw, out);
-    else
-        hipLaunchKernelGGL(k_wgrad_narrow_s3<3>, grid, dim3(256), 0, st, dz, ldz, x, ldx, xoff, cin, cout, B, H, W, ppw, out);
-    if (prof_enabled()) prof_pop(st);
+    const auto fn = 9 * cin <= 32 ? k_wgrad_narrow_s3<1> : 9 * cin <= 64 ? k_wgrad_narrow_s3<2> : k_wgrad_narrow_s3<3>;
+    launch_prof(fn, "cad::k_wgrad_narrow_s3", 2.0 * M * per, grid, st, dz, ldz, x, ldx, xoff, cin, cout, B, H, W, ppw, out);
     if (s > 1) finish_slabs(slab, s, per, dw, st);
     return true;
 }
@@ -844,27 +765,148 @@ void launch_wgrad_win(GemmArgs& a, float* dw, float* slab, int64_t slab_cap, int
     a.ldc = a.N; a.slab_stride = per;
     a.C = s == 1 ? dw : slab;
     const dim3 grid(a.M / 64, cin / 64, s);
-    const char* name = strip ? "void cad::k_conv3x3_wgrad_strip_s3(cad::GemmArgs)" : "void cad::k_conv3x3_wgrad_win_s3(cad::GemmArgs)";
-    if (prof_enabled()) prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-    if (strip) hipLaunchKernelGGL(k_conv3x3_wgrad_strip_s3, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_conv3x3_wgrad_win_s3, grid, dim3(256), 0, st, a);
-    if (prof_enabled()) prof_pop(st);
+    if (strip) launch_gemm(k_conv3x3_wgrad_strip_s3, KName{"k_conv3x3_wgrad_strip_s3"}, grid, a, st);
+    else launch_gemm(k_conv3x3_wgrad_win_s3, KName{"k_conv3x3_wgrad_win_s3"}, grid, a, st);
     if (s > 1) finish_slabs(slab, s, per, dw, st);
 }
 
-// weight-gradient GEMM (M x N over K = pixels): split-K slabs, then the deterministic reduction
-template <template <int, int, int> class F, template <int, int, int> class T3, template <int, int, int> class TB>
-void launch_wgrad(GemmArgs& a, float* dw, float* slab, int64_t slab_cap, int64_t kbytes, hipStream_t st) {
-    const Cfg c = pick_cfg(a.M, a.N);
-    const int kb = engine() == 1 ? kS3KB : engine() == 2 ? kB1KB : 16;
+// split-K plan of a weight-gradient GEMM (M x N over K = pixels) at stage depth kb: sets the slab fields of
+// `a` and returns the slab count; more than one: finish_slabs after the launch
+int plan_slabs(GemmArgs& a, Cfg c, int kb, float* dw, float* slab, int64_t slab_cap, int64_t kbytes) {
     int s = plan_splits(a, c, kb, slab_cap, kbytes);
     a.kstages_per_split = cdiv(cdiv(a.K, kb), s);
     s = cdiv(cdiv(a.K, kb), a.kstages_per_split);
-    const int64_t per = (int64_t)a.M * a.N;
-    a.ldc = a.N; a.slab_stride = per;
+    a.ldc = a.N; a.slab_stride = (int64_t)a.M * a.N;
     a.C = s == 1 ? dw : slab;
+    return s;
+}
+// ... on the current engine with in-loader operand conversion
+template <class F, class T3, class TB>
+void launch_wgrad(GemmArgs& a, float* dw, float* slab, int64_t slab_cap, int64_t kbytes, hipStream_t st) {
+    const Cfg c = pick_cfg(a.M, a.N);
+    const int kb = engine() == 1 ? kS3KB : engine() == 2 ? kB1KB : 16;
+    const int s = plan_slabs(a, c, kb, dw, slab, slab_cap, kbytes);
     launch_on_engine<F, T3, TB>(c, kb, a, s, st);
-    if (s > 1) finish_slabs(slab, s, per, dw, st);
+    if (s > 1) finish_slabs(slab, s, a.slab_stride, dw, st);
+}
+// ... of family K on the pre-split twins
+template <class K>
+void launch_wgrad_ps(GemmArgs& a, float* dw, float* slab, int64_t slab_cap, int64_t kbytes, hipStream_t st) {
+    const Cfg c = pick_cfg(a.M, a.N);
+    const int kb = ps_kb(false, c);
+    const int s = plan_slabs(a, c, kb, dw, slab, slab_cap, kbytes);
+    launch_kb<K, 32>(c, kb, a, s, st);
+    if (s > 1) finish_slabs(slab, s, a.slab_stride, dw, st);
+}
+
+// ---- GemmArgs of each contraction.  Operands are Split views (kernels.hpp): fp32 rows for the engines
+// that convert in their loaders, bf16 twins for the pre-split kernels. ----
+GemmArgs gemm_args(int M, int N, int K, int B, int H, int W, Split a_, Split b_) {
+    GemmArgs a{};
+    a.M = M; a.N = N; a.K = K;
+    a.B = B; a.H = H; a.W = W;
+    a.A = (const float*)a_.p; a.lda = a_.ld; a.a_coff = a_.coff;
+    a.Bm = (const float*)b_.p; a.ldb = b_.ld; a.b_coff = b_.coff;
+    return a;
+}
+void out_args(GemmArgs& a, void* y, int64_t ldy, int ycoff) {
+    a.C = static_cast<float*>(y); a.ldc = ldy; a.c_coff = ycoff;
+}
+// 3 x 3 convolution: y[pixel][n] = sum over (tap, ci) of im2col(x)[pixel][tap, ci] w[n][tap, ci].  Forward:
+// n = cout; input gradient: the same contraction of dz with the repacked weights, cin and cout swapped.
+GemmArgs conv3x3_args(Split x, int cin, Split w, int n, void* y, int64_t ldy, int ycoff, int B, int H, int W) {
+    GemmArgs a = gemm_args(B * H * W, n, 9 * cin, B, H, W, x, w);
+    a.a_cin = cin;
+    out_args(a, y, ldy, ycoff);
+    return a;
+}
+// ConvTranspose2d(k2, s2) forward: [pixel][cin] x wf[(q, co)][cin], pixel-shuffled by the epilogue
+GemmArgs convT_fwd_args(Split x, int cin, Split wf, const float* bias, int cout, void* y, int64_t ldy, int ycoff, int B,
+                        int H, int W) {
+    GemmArgs a = gemm_args(B * H * W, 4 * cout, cin, B, H, W, x, wf);
+    out_args(a, y, ldy, ycoff);
+    a.bias = bias;
+    return a;
+}
+// ... input gradient: the up-gather of g over (q, co) x wm[ci][(q, co)]
+GemmArgs convT_dgrad_args(Split g, int cout, Split wm, int cin, void* dx, int B, int H, int W) {
+    GemmArgs a = gemm_args(B * H * W, cin, 4 * cout, B, H, W, g, wm);
+    a.a_cin = cout;
+    out_args(a, dx, cin, 0);
+    return a;
+}
+// weight gradients: dw[m][n] = sum over pixels of a_[pixel][m] gather(b_)[pixel][n] (b_cin: channels per tap /
+// quadrant of the gathered operand); the output fields are plan_slabs'
+GemmArgs wgrad_args(Split a_, int M, Split b_, int N, int b_cin, int B, int H, int W) {
+    GemmArgs a = gemm_args(M, N, B * H * W, B, H, W, a_, b_);
+    a.b_cin = b_cin;
+    return a;
+}
+
+// ---- epilogue selectors: f(Epi{}) with the epilogue a request asks for, among the ones a kernel family
+// is built with ----
+// conv3x3 forward: plain store / BN partials / eval-mode activation, fp32 or (OB16: the pre-split kernels
+// only) bf16 rows
+template <bool OB16, class F>
+void with_fwd_epi(const ConvEpi& e, F&& f) {
+    if (e.act && e.act->gam) f(EpiStoreAct<OB16, true>{});
+    else if (e.act) f(EpiStoreAct<OB16, false>{});
+    else if (e.stats) f(std::conditional_t<OB16, EpiStoreStatsB16, EpiStoreStats>{});
+    else f(std::conditional_t<OB16, EpiStoreB16, EpiStore>{});
+}
+// conv3x3 input gradient on the pre-split twins: fp32 or bf16 rows; SPLIT (the window kernels only): the
+// split stores
+template <bool SPLIT, class F>
+void with_dgrad_epi(bool b16, bool split, F&& f) {
+    if (split) {
+        if constexpr (SPLIT) {
+            if (b16) f(EpiStoreSplit2B16{});
+            else f(EpiStoreSplitB16{});
+        } else {
+            throw std::runtime_error("conv3x3_dgrad_ps: the split store is not built for the im2col kernels");
+        }
+    } else if (b16) {
+        f(EpiStoreB16{});
+    } else {
+        f(EpiStore{});
+    }
+}
+// dense forward: plain / BN partials, fp32 or bf16 rows, or the added matrix (fp32 rows, no partials); DMA
+// (the LDS-DMA kernel only): the added matrix of its own stride, or masked
+template <bool DMA, class F>
+void with_dense_epi(bool add, bool add_ld, bool mask, bool stats, bool b16, F&& f) {
+    if (add) {
+        if (stats || b16) throw std::runtime_error("dense GEMM: the added matrix needs fp32 output");
+        if constexpr (DMA) {
+            if (mask) return f(EpiStoreAddMask{});
+            if (add_ld) return f(EpiStoreAddLd{});
+        }
+        f(EpiStoreAdd{});
+    } else if (b16) {
+        if (stats) f(EpiStoreStatsB16{});
+        else f(EpiStoreB16{});
+    } else {
+        if (stats) f(EpiStoreStats{});
+        else f(EpiStore{});
+    }
+}
+
+void act_check(const ActCoeffs& act, int H, int W) {
+    if (!act.scale || !act.shift || !act.gam != !act.bet) throw std::invalid_argument("conv3x3_fwd_act: coefficient pointers");
+    // the row-major epilogue takes a 4-row group's sample from its first row
+    if ((int64_t)H * W % 4) throw std::invalid_argument("conv3x3_fwd_act: H * W must be a multiple of 4");
+}
+// the request's activation coefficients, checked and set in `a` (none: all null), with the BN partials
+const ActCoeffs& epi_args(GemmArgs& a, const ConvEpi& e) {
+    static const ActCoeffs none{};
+    const ActCoeffs& act = e.act ? *e.act : none;
+    a.stats = e.stats;
+    a.bn_scale = act.scale; a.bn_shift = act.shift; a.act_gam = act.gam; a.act_bet = act.bet;
+    return act;
+}
+void epi_check(const ConvEpi& e, int H, int W) {
+    if (e.act && e.stats) throw std::invalid_argument("conv3x3_fwd: BN partials and the activation epilogue exclude each other");
+    if (e.act) act_check(*e.act, H, W);
 }
 }  // namespace
 
@@ -889,109 +931,85 @@ bool conv3x3_wtwin_on() {
 }
 
 void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y,
-                 int64_t ldy, int ycoff, int B, int H, int W, float* stats, hipStream_t st, const void* wtwin) {
-    CAD_NO_ALIAS("conv3x3_fwd", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, 4, "y")},
-                 {aview(x, (int64_t)B * H * W, ldx, xcoff, cin, 4, "x"), aview(w, cout, 9 * cin, 0, 9 * cin, 4, "w"),
-                  aview(wtwin, 1, conv3x3_wtwin_bytes(cin, cout), 0, wtwin ? conv3x3_wtwin_bytes(cin, cout) : 0, 1, "wtwin")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cout; a.K = 9 * cin;
-    a.B = B; a.H = H; a.W = W;
-    a.A = x; a.lda = ldx; a.a_coff = xcoff; a.a_cin = cin;
-    a.Bm = w; a.ldb = 9 * cin; a.b_coff = 0;
-    a.C = y; a.ldc = ldy; a.c_coff = ycoff;
-    a.stats = stats;
-    if (const WinPick w = pick_win(cin, W, cout); w.R) {
-        a.wtwin = wtwin;
-        if (stats) launch_win<EpiStoreStats>(w, a, st);
-        else launch_win<EpiStore>(w, a, st);
-        return;
-    }
-    const Cfg c = pick_cfg(a.M, a.N);
-    if (stats) launch_engine<KConvFwdS, KConvFwdS3, KConvFwdSB>(c, true, a, st);
-    else launch_engine<KConvFwd, KConvFwd3, KConvFwdB>(c, true, a, st);
-}
-
-namespace {
-void act_check(const ActCoeffs& act, int H, int W) {
-    if (!act.scale || !act.shift || !act.gam != !act.bet) throw std::invalid_argument("conv3x3_fwd_act: coefficient pointers");
-    // the row-major epilogue takes a 4-row group's sample from its first row
-    if ((int64_t)H * W % 4) throw std::invalid_argument("conv3x3_fwd_act: H * W must be a multiple of 4");
-}
-void act_args(GemmArgs& a, const ActCoeffs& act) {
-    a.bn_scale = act.scale; a.bn_shift = act.shift; a.act_gam = act.gam; a.act_bet = act.bet;
-}
-}  // namespace
-
-void conv3x3_fwd_act(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y, int64_t ldy,
-                     int ycoff, int B, int H, int W, const ActCoeffs& act, hipStream_t st, const void* wtwin) {
-    act_check(act, H, W);
-    CAD_NO_ALIAS("conv3x3_fwd_act", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, 4, "y")},
+                 int64_t ldy, int ycoff, int B, int H, int W, ConvEpi epi, hipStream_t st, const void* wtwin) {
+    epi_check(epi, H, W);
+    GemmArgs a = conv3x3_args(Split{x, ldx, xcoff}, cin, Split{w, 9 * cin, 0}, cout, y, ldy, ycoff, B, H, W);
+    const ActCoeffs& act = epi_args(a, epi);
+    CAD_NO_ALIAS(epi.act ? "conv3x3_fwd_act" : "conv3x3_fwd", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, 4, "y")},
                  {aview(x, (int64_t)B * H * W, ldx, xcoff, cin, 4, "x"), aview(w, cout, 9 * cin, 0, 9 * cin, 4, "w"),
                   aview(wtwin, 1, conv3x3_wtwin_bytes(cin, cout), 0, wtwin ? conv3x3_wtwin_bytes(cin, cout) : 0, 1, "wtwin"),
                   aview(act.scale, 1, cout, 0, cout, 4, "scale"), aview(act.shift, 1, cout, 0, cout, 4, "shift"),
                   aview(act.gam, B, cout, 0, act.gam ? cout : 0, 4, "gamma"),
                   aview(act.bet, B, cout, 0, act.bet ? cout : 0, 4, "beta")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cout; a.K = 9 * cin;
-    a.B = B; a.H = H; a.W = W;
-    a.A = x; a.lda = ldx; a.a_coff = xcoff; a.a_cin = cin;
-    a.Bm = w; a.ldb = 9 * cin; a.b_coff = 0;
-    a.C = y; a.ldc = ldy; a.c_coff = ycoff;
-    act_args(a, act);
-    if (const WinPick wp = pick_win(cin, W, cout); wp.R) {
-        a.wtwin = wtwin;
-        if (act.gam) launch_win<EpiStoreAct<false, true>>(wp, a, st);
-        else launch_win<EpiStoreAct<false, false>>(wp, a, st);
-        return;
-    }
-    const Cfg c = pick_cfg(a.M, a.N);
-    if (act.gam) launch_engine<KConvFwdActF, KConvFwdActF3, KConvFwdActFB>(c, true, a, st);
-    else launch_engine<KConvFwdAct, KConvFwdAct3, KConvFwdActB>(c, true, a, st);
+    const WinPick wp = pick_win(cin, W, cout);
+    if (wp.R) a.wtwin = wtwin;
+    with_fwd_epi<false>(epi, [&](auto e) {
+        using Epi = decltype(e);
+        if (wp.R) launch_win<Epi>(wp, a, st);
+        else launch_engine<KConvFwdF<Epi>, KConvFwd3<Epi>, KConvFwdB<Epi>>(pick_cfg(a.M, a.N), true, a, st);
+    });
 }
 
 void convT_fwd(const float* x, int64_t ldx, int cin, const float* wf, const float* bias, int cout,
                float* y, int64_t ldy, int ycoff, int B, int H, int W, hipStream_t st) {
     CAD_NO_ALIAS("convT_fwd", {aview(y, (int64_t)B * 4 * H * W, ldy, ycoff, cout, 4, "y")},
                  {aview(x, (int64_t)B * H * W, ldx, 0, cin, 4, "x"), aview(wf, 4 * cout, cin, 0, cin, 4, "w")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = 4 * cout; a.K = cin;
-    a.B = B; a.H = H; a.W = W;
-    a.A = x; a.lda = ldx; a.a_coff = 0;
-    a.Bm = wf; a.ldb = cin;
-    a.C = y; a.ldc = ldy; a.c_coff = ycoff; a.bias = bias;
-    launch_engine<KConvTFwd, KConvTFwd3, KConvTFwdB>(pick_cfg(a.M, a.N), false, a, st);
+    GemmArgs a = convT_fwd_args(Split{x, ldx, 0}, cin, Split{wf, cin, 0}, bias, cout, y, ldy, ycoff, B, H, W);
+    launch_engine<KConvTFwdF<>, KConvTFwd3<>, KConvTFwdB<>>(pick_cfg(a.M, a.N), false, a, st);
 }
+
+namespace {
+// conv2's input gradient with bn1's backward column sums from the window epilogue (EpiStoreBnSums):
+// returns the number of tiles whose partials it wrote (0: the partials do not fit; nothing launched)
+template <bool OB16, bool PS>
+int dgrad_bnsums_launch(const WinPick& wp, GemmArgs& a, const BnSums& bn, hipStream_t st) {
+    const int tiles = win_blocks(wp, a.B, a.H, a.W);
+    if (!bn.part || (int64_t)tiles * 2 * a.N > bn.part_cap) return 0;
+    a.bn_g = bn.y; a.bn_ldg = bn.ldy;
+    a.bn_mean = bn.mean; a.bn_invstd = bn.invstd; a.bn_scale = bn.scale; a.bn_shift = bn.shift;
+    a.bn_part = bn.part;
+    if (bn.y_bf16) launch_win<EpiStoreBnSums<OB16, true>, PS>(wp, a, st);
+    else launch_win<EpiStoreBnSums<OB16, false>, PS>(wp, a, st);
+    return tiles;
+}
+// conv3x3_dgrad (bn == nullptr) and conv3x3_dgrad_bnsums (the window kernels only) on fp32 operands
+int dgrad_f32(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx, int B, int H, int W,
+              const BnSums* bn, hipStream_t st, const void* wtwin) {
+    const WinPick wp = pick_win(cout, W, cin);
+    if (bn && (!wp.R || bn->y_bf16)) return 0;
+    if (!bn)
+        CAD_NO_ALIAS("conv3x3_dgrad", {aview(dx, (int64_t)B * H * W, lddx, 0, cin, 4, "dx")},
+                     {aview(dz, (int64_t)B * H * W, cout, 0, cout, 4, "dz"), aview(wd, cin, 9 * cout, 0, 9 * cout, 4, "w"),
+                      aview(wtwin, 1, conv3x3_wtwin_bytes(cout, cin), 0, wtwin ? conv3x3_wtwin_bytes(cout, cin) : 0, 1, "wtwin")});
+    GemmArgs a = conv3x3_args(Split{dz, cout, 0}, cout, Split{wd, 9 * cout, 0}, cin, dx, lddx, 0, B, H, W);
+    if (wp.R) a.wtwin = wtwin;
+    if (bn) return dgrad_bnsums_launch<false, false>(wp, a, *bn, st);
+    if (wp.R) launch_win<EpiStore>(wp, a, st);
+    else launch_engine<KConvFwdF<EpiStore>, KConvFwd3<EpiStore>, KConvFwdB<EpiStore>>(pick_cfg(a.M, a.N), true, a, st);
+    return 0;
+}
+}  // namespace
 
 void conv3x3_dgrad(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx,
                    int B, int H, int W, hipStream_t st, const void* wtwin) {
-    CAD_NO_ALIAS("conv3x3_dgrad", {aview(dx, (int64_t)B * H * W, lddx, 0, cin, 4, "dx")},
-                 {aview(dz, (int64_t)B * H * W, cout, 0, cout, 4, "dz"), aview(wd, cin, 9 * cout, 0, 9 * cout, 4, "w"),
-                  aview(wtwin, 1, conv3x3_wtwin_bytes(cout, cin), 0, wtwin ? conv3x3_wtwin_bytes(cout, cin) : 0, 1, "wtwin")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cin; a.K = 9 * cout;
-    a.B = B; a.H = H; a.W = W;
-    a.A = dz; a.lda = cout; a.a_coff = 0; a.a_cin = cout;
-    a.Bm = wd; a.ldb = 9 * cout;
-    a.C = dx; a.ldc = lddx; a.c_coff = 0;
-    if (const WinPick w = pick_win(cout, W, cin); w.R) {
-        a.wtwin = wtwin;
-        launch_win<EpiStore>(w, a, st);
-        return;
-    }
-    launch_engine<KConvFwd, KConvFwd3, KConvFwdB>(pick_cfg(a.M, a.N), true, a, st);
+    dgrad_f32(dz, cout, wd, cin, dx, lddx, B, H, W, nullptr, st, wtwin);
+}
+// S3 engine only: measured on MI355X (tools/ab_step.py, same box) fp32 configs[1] 225.7 -> 223.9 ms/step; the
+// bf16 engine's form (bf16 dL/da1, the same epilogue on the B1 window kernels) made configs[3] 64.1 -> 68.2
+// ms/step — the per-element y load and fp64 sums in the epilogue cost its cheap GEMMs more than the
+// column-reduction pass they replace.  Returns 0 (nothing launched, the caller takes the unfused path) when no
+// window kernel serves the shape or the partials do not fit.
+int conv3x3_dgrad_bnsums(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx, int B, int H,
+                         int W, const BnSums& bn, hipStream_t st, const void* wtwin) {
+    return dgrad_f32(dz, cout, wd, cin, dx, lddx, B, H, W, &bn, st, wtwin);
 }
 
 void convT_dgrad(const float* g, int64_t ldg, int gcoff, int cout, const float* wm, int cin, float* dx,
                  int B, int H, int W, hipStream_t st) {
     CAD_NO_ALIAS("convT_dgrad", {aview(dx, (int64_t)B * H * W, cin, 0, cin, 4, "dx")},
                  {aview(g, (int64_t)B * 4 * H * W, ldg, gcoff, cout, 4, "g"), aview(wm, cin, 4 * cout, 0, 4 * cout, 4, "w")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cin; a.K = 4 * cout;
-    a.B = B; a.H = H; a.W = W;
-    a.A = g; a.lda = ldg; a.a_coff = gcoff; a.a_cin = cout;
-    a.Bm = wm; a.ldb = 4 * cout;
-    a.C = dx; a.ldc = cin; a.c_coff = 0;
-    launch_engine<KConvTDgrad, KConvTDgrad3, KConvTDgradB>(pick_cfg(a.M, a.N), false, a, st);
+    GemmArgs a = convT_dgrad_args(Split{g, ldg, gcoff}, cout, Split{wm, 4 * cout, 0}, cin, dx, B, H, W);
+    launch_engine<KConvTDgradF<>, KConvTDgrad3<>, KConvTDgradB<>>(pick_cfg(a.M, a.N), false, a, st);
 }
 
 int64_t wgrad_slab_floats(int M, int N, int Kpix) {
@@ -1005,17 +1023,13 @@ void conv3x3_wgrad(const float* dz, int cout, const float* x, int64_t ldx, int x
     CAD_NO_ALIAS("conv3x3_wgrad",
                  {aview(dw, cout, 9 * cin, 0, 9 * cin, 4, "dw"), aview(slab, 1, slab_cap, 0, slab ? slab_cap : 0, 4, "slab")},
                  {aview(dz, (int64_t)B * H * W, cout, 0, cout, 4, "dz"), aview(x, (int64_t)B * H * W, ldx, xcoff, cin, 4, "x")});
-    GemmArgs a{};
-    a.M = cout; a.N = 9 * cin; a.K = B * H * W;
-    a.B = B; a.H = H; a.W = W;
-    a.A = dz; a.lda = cout; a.a_coff = 0;
-    a.Bm = x; a.ldb = ldx; a.b_coff = xcoff; a.b_cin = cin;
+    GemmArgs a = wgrad_args(Split{dz, cout, 0}, cout, Split{x, ldx, xcoff}, 9 * cin, cin, B, H, W);
     if (use_wgrad_win(cout, cin, W)) {
         launch_wgrad_win(a, dw, slab, slab_cap, 4 * std::max<int64_t>(a.lda, ldx), st);
         return;
     }
     if (wgrad_narrow_s3(dz, cout, x, ldx, xcoff, cin, cout, dw, B, H, W, slab, slab_cap, st)) return;
-    launch_wgrad<KConvWgrad, KConvWgrad3, KConvWgradB>(a, dw, slab, slab_cap, 4 * std::max<int64_t>(a.lda, ldx), st);
+    launch_wgrad<KConvWgradF<>, KConvWgrad3<>, KConvWgradB<>>(a, dw, slab, slab_cap, 4 * std::max<int64_t>(a.lda, ldx), st);
 }
 
 void convT_wgrad(const float* x, int cin, const float* g, int64_t ldg, int gcoff, int cout, float* dw,
@@ -1023,12 +1037,8 @@ void convT_wgrad(const float* x, int cin, const float* g, int64_t ldg, int gcoff
     CAD_NO_ALIAS("convT_wgrad",
                  {aview(dw, cin, 4 * cout, 0, 4 * cout, 4, "dw"), aview(slab, 1, slab_cap, 0, slab ? slab_cap : 0, 4, "slab")},
                  {aview(x, (int64_t)B * H * W, cin, 0, cin, 4, "x"), aview(g, (int64_t)B * 4 * H * W, ldg, gcoff, cout, 4, "g")});
-    GemmArgs a{};
-    a.M = cin; a.N = 4 * cout; a.K = B * H * W;
-    a.B = B; a.H = H; a.W = W;
-    a.A = x; a.lda = cin; a.a_coff = 0;
-    a.Bm = g; a.ldb = ldg; a.b_coff = gcoff; a.b_cin = cout;
-    launch_wgrad<KConvTWgrad, KConvTWgrad3, KConvTWgradB>(a, dw, slab, slab_cap, 4 * std::max<int64_t>(a.lda, 4 * ldg),
+    GemmArgs a = wgrad_args(Split{x, cin, 0}, cin, Split{g, ldg, gcoff}, 4 * cout, cout, B, H, W);
+    launch_wgrad<KConvTWgradF<>, KConvTWgrad3<>, KConvTWgradB<>>(a, dw, slab, slab_cap, 4 * std::max<int64_t>(a.lda, 4 * ldg),
                                                            st);
 }
 
@@ -1056,117 +1066,40 @@ void ps_check(const Split& s, int channels, const char* what) {
 }
 }  // namespace
 
-void conv3x3_fwd_ps(Split x, int cin, Split w, int cout, float* y, int64_t ldy, int ycoff, int B, int H, int W,
-                    float* stats, hipStream_t st, bool y_bf16) {
-    ps_check(x, cin, "conv3x3_fwd x");
-    ps_check(w, 9 * cin, "conv3x3_fwd w");
-    CAD_NO_ALIAS("conv3x3_fwd_ps", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, y_bf16 ? 2 : 4, "y")},
-                 {aview(x.p, (int64_t)B * H * W, x.ld, x.coff, cin, 2, "x"), aview(w.p, cout, w.ld, w.coff, 9 * cin, 2, "w")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cout; a.K = 9 * cin;
-    a.B = B; a.H = H; a.W = W;
-    a.A = (const float*)x.p; a.lda = x.ld; a.a_coff = x.coff; a.a_cin = cin;
-    a.Bm = (const float*)w.p; a.ldb = w.ld; a.b_coff = w.coff;
-    a.C = y; a.ldc = ldy; a.c_coff = ycoff;
-    a.stats = stats;
-    if (const WinPick wp = pick_win_ps(cin, W, cout, x.coff); wp.R && w.coff == 0) {
-        if (y_bf16) {
-            if (stats) launch_win<EpiStoreStatsB16, true>(wp, a, st);
-            else launch_win<EpiStoreB16, true>(wp, a, st);
-        } else {
-            if (stats) launch_win<EpiStoreStats, true>(wp, a, st);
-            else launch_win<EpiStore, true>(wp, a, st);
-        }
-        return;
-    }
+namespace {
+// the im2col conv3x3 forward / dgrad on the pre-split twins
+template <class Epi>
+void conv3x3_im2col_ps(GemmArgs& a, hipStream_t st) {
     const Cfg c = pick_cfg(a.M, a.N);
     const int kb = ps_kb(true, c);
     a.kstages_per_split = cdiv(a.K, kb);
     // channel-major K order: the nine taps of a channel block re-read the same input rows back to back
-    a.cimajor = cin % kb == 0;
-    if (y_bf16) {
-        if (stats) launch_kb<KConvFwdSP1B, 32, 64>(c, kb, a, 1, st);
-        else launch_kb<KConvFwdP1B, 32, 64>(c, kb, a, 1, st);
-    } else {
-        if (stats) launch_kb<KConvFwdSP1, 32, 64>(c, kb, a, 1, st);
-        else launch_kb<KConvFwdP1, 32, 64>(c, kb, a, 1, st);
-    }
+    a.cimajor = a.a_cin % kb == 0;
+    launch_kb<KConvFwdP1<Epi>, 32, 64>(c, kb, a, 1, st);
 }
+}  // namespace
 
-void conv3x3_fwd_ps_act(Split x, int cin, Split w, int cout, void* y, int64_t ldy, int ycoff, int B, int H, int W,
-                        const ActCoeffs& act, hipStream_t st, bool y_bf16) {
-    ps_check(x, cin, "conv3x3_fwd_act x");
-    ps_check(w, 9 * cin, "conv3x3_fwd_act w");
-    act_check(act, H, W);
-    CAD_NO_ALIAS("conv3x3_fwd_ps_act", {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, y_bf16 ? 2 : 4, "y")},
+void conv3x3_fwd_ps(Split x, int cin, Split w, int cout, void* y, int64_t ldy, int ycoff, int B, int H, int W,
+                    ConvEpi epi, hipStream_t st, bool y_bf16) {
+    ps_check(x, cin, epi.act ? "conv3x3_fwd_act x" : "conv3x3_fwd x");
+    ps_check(w, 9 * cin, epi.act ? "conv3x3_fwd_act w" : "conv3x3_fwd w");
+    epi_check(epi, H, W);
+    GemmArgs a = conv3x3_args(x, cin, w, cout, y, ldy, ycoff, B, H, W);
+    const ActCoeffs& act = epi_args(a, epi);
+    CAD_NO_ALIAS(epi.act ? "conv3x3_fwd_ps_act" : "conv3x3_fwd_ps",
+                 {aview(y, (int64_t)B * H * W, ldy, ycoff, cout, y_bf16 ? 2 : 4, "y")},
                  {aview(x.p, (int64_t)B * H * W, x.ld, x.coff, cin, 2, "x"), aview(w.p, cout, w.ld, w.coff, 9 * cin, 2, "w"),
                   aview(act.scale, 1, cout, 0, cout, 4, "scale"), aview(act.shift, 1, cout, 0, cout, 4, "shift"),
                   aview(act.gam, B, cout, 0, act.gam ? cout : 0, 4, "gamma"),
                   aview(act.bet, B, cout, 0, act.bet ? cout : 0, 4, "beta")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cout; a.K = 9 * cin;
-    a.B = B; a.H = H; a.W = W;
-    a.A = (const float*)x.p; a.lda = x.ld; a.a_coff = x.coff; a.a_cin = cin;
-    a.Bm = (const float*)w.p; a.ldb = w.ld; a.b_coff = w.coff;
-    a.C = static_cast<float*>(y); a.ldc = ldy; a.c_coff = ycoff;
-    act_args(a, act);
-    const bool film = act.gam != nullptr;
-    if (const WinPick wp = pick_win_ps(cin, W, cout, x.coff); wp.R && w.coff == 0) {
-        if (y_bf16) {
-            if (film) launch_win<EpiStoreAct<true, true>, true>(wp, a, st);
-            else launch_win<EpiStoreAct<true, false>, true>(wp, a, st);
-        } else {
-            if (film) launch_win<EpiStoreAct<false, true>, true>(wp, a, st);
-            else launch_win<EpiStoreAct<false, false>, true>(wp, a, st);
-        }
-        return;
-    }
-    const Cfg c = pick_cfg(a.M, a.N);
-    const int kb = ps_kb(true, c);
-    a.kstages_per_split = cdiv(a.K, kb);
-    a.cimajor = cin % kb == 0;
-    if (y_bf16) {
-        if (film) launch_kb<KConvFwdActFOP1, 32, 64>(c, kb, a, 1, st);
-        else launch_kb<KConvFwdActOP1, 32, 64>(c, kb, a, 1, st);
-    } else {
-        if (film) launch_kb<KConvFwdActFP1, 32, 64>(c, kb, a, 1, st);
-        else launch_kb<KConvFwdActP1, 32, 64>(c, kb, a, 1, st);
-    }
-}
-
-// conv2's input gradient with bn1's backward column sums from the window epilogue (EpiStoreBnSums):
-// returns the number of tiles whose partials it wrote (0: no window kernel for this shape or the
-// partials do not fit; nothing launched, the caller takes the unfused path).  S3 engine only: measured
-// on MI355X (tools/ab_step.py, same box) fp32 configs[1] 225.7 -> 223.9 ms/step; the bf16 engine's
-// form (bf16 dL/da1, the same epilogue on the B1 window kernels) made configs[3] 64.1 -> 68.2 ms/step —
-// the per-element y load and fp64 sums in the epilogue cost its cheap GEMMs more than the
-// column-reduction pass they replace
-namespace {
-template <bool OB16, bool PS>
-int dgrad_bnsums_launch(const WinPick& wp, GemmArgs& a, const BnSums& bn, hipStream_t st) {
-    const int tiles = win_blocks(wp, a.B, a.H, a.W);
-    if (!bn.part || (int64_t)tiles * 2 * a.N > bn.part_cap) return 0;
-    a.bn_g = bn.y; a.bn_ldg = bn.ldy;
-    a.bn_mean = bn.mean; a.bn_invstd = bn.invstd; a.bn_scale = bn.scale; a.bn_shift = bn.shift;
-    a.bn_part = bn.part;
-    if (bn.y_bf16) launch_win<EpiStoreBnSums<OB16, true>, PS>(wp, a, st);
-    else launch_win<EpiStoreBnSums<OB16, false>, PS>(wp, a, st);
-    return tiles;
-}
-}  // namespace
-
-int conv3x3_dgrad_bnsums(const float* dz, int cout, const float* wd, int cin, float* dx, int64_t lddx, int B, int H,
-                         int W, const BnSums& bn, hipStream_t st, const void* wtwin) {
-    const WinPick w = pick_win(cout, W, cin);
-    if (!w.R || bn.y_bf16) return 0;
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cin; a.K = 9 * cout;
-    a.B = B; a.H = H; a.W = W;
-    a.A = dz; a.lda = cout; a.a_coff = 0; a.a_cin = cout;
-    a.Bm = wd; a.ldb = 9 * cout;
-    a.C = dx; a.ldc = lddx; a.c_coff = 0;
-    a.wtwin = wtwin;
-    return dgrad_bnsums_launch<false, false>(w, a, bn, st);
+    const WinPick wp = pick_win_ps(cin, W, cout, x.coff);
+    auto launch = [&](auto e) {
+        using Epi = decltype(e);
+        if (wp.R && w.coff == 0) launch_win<Epi, true>(wp, a, st);
+        else conv3x3_im2col_ps<Epi>(a, st);
+    };
+    if (y_bf16) with_fwd_epi<true>(epi, launch);
+    else with_fwd_epi<false>(epi, launch);
 }
 
 bool conv3x3_dgrad_split_ok(Split dz, int cout, Split wd, int cin, int W, int split_n) {
@@ -1187,29 +1120,15 @@ bool conv3x3_dgrad_ps(Split dz, int cout, Split wd, int cin, float* dx, int64_t 
                  {aview(dx, (int64_t)B * H * W, lddx, 0, hi ? split_n : cin, dx_bf16 ? 2 : 4, "dx"),
                   aview(hi, (int64_t)B * H * W, ldhi, 0, hi ? cin - split_n : 0, 2, "hi (split store)")},
                  {aview(dz.p, (int64_t)B * H * W, dz.ld, dz.coff, cout, 2, "dz"), aview(wd.p, cin, wd.ld, wd.coff, 9 * cout, 2, "w")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cin; a.K = 9 * cout;
-    a.B = B; a.H = H; a.W = W;
-    a.A = (const float*)dz.p; a.lda = dz.ld; a.a_coff = dz.coff; a.a_cin = cout;
-    a.Bm = (const float*)wd.p; a.ldb = wd.ld; a.b_coff = wd.coff;
-    a.C = dx; a.ldc = lddx; a.c_coff = 0;
+    GemmArgs a = conv3x3_args(dz, cout, wd, cin, dx, lddx, 0, B, H, W);
     if (const WinPick wp = pick_win_ps(cout, W, cin, dz.coff); wp.R && wd.coff == 0) {
         if (hi) {
             a.C2 = hi; a.ldc2 = ldhi; a.split_n = split_n;
-            if (dx_bf16) launch_win<EpiStoreSplit2B16, true>(wp, a, st);
-            else launch_win<EpiStoreSplitB16, true>(wp, a, st);
-            return true;
         }
-        if (dx_bf16) launch_win<EpiStoreB16, true>(wp, a, st);
-        else launch_win<EpiStore, true>(wp, a, st);
-        return false;
+        with_dgrad_epi<true>(dx_bf16, hi != nullptr, [&](auto e) { launch_win<decltype(e), true>(wp, a, st); });
+        return hi != nullptr;
     }
-    const Cfg c = pick_cfg(a.M, a.N);
-    const int kb = ps_kb(true, c);
-    a.kstages_per_split = cdiv(a.K, kb);
-    a.cimajor = cout % kb == 0;
-    if (dx_bf16) launch_kb<KConvFwdP1B, 32, 64>(c, kb, a, 1, st);
-    else launch_kb<KConvFwdP1, 32, 64>(c, kb, a, 1, st);
+    with_dgrad_epi<false>(dx_bf16, hi != nullptr, [&](auto e) { conv3x3_im2col_ps<decltype(e)>(a, st); });
     return false;
 }
 
@@ -1300,19 +1219,11 @@ void launch_wgrad_win_ps1(GemmArgs& a, float* dw, float* slab, int64_t slab_cap,
     a.ldc = a.N; a.slab_stride = per;
     a.C = s == 1 ? dw : slab;
     const dim3 grid(a.M / 64, cin / 64, s);
-    const int nbuf = wg_nbuf();
-    char name[96];
-    if (strip2) std::snprintf(name, sizeof name, "void cad::k_conv3x3_wgrad_strip2_bf16d<%d>(cad::GemmArgs)", P);
-    else if (strip) std::snprintf(name, sizeof name, "void cad::k_conv3x3_wgrad_strip_bf16d<%d>(cad::GemmArgs)", P);
-    else if (dma) std::snprintf(name, sizeof name, "void cad::k_conv3x3_wgrad_win_bf16d<%d, %d>(cad::GemmArgs)", P, nbuf);
-    else std::snprintf(name, sizeof name, "void cad::k_conv3x3_wgrad_win_bf16p<%d>(cad::GemmArgs)", P);
-    if (prof_enabled()) prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-    if (strip2) hipLaunchKernelGGL(k_conv3x3_wgrad_strip2_bf16d<P == 32 ? 32 : 16>, grid, dim3(256), 0, st, a);
-    else if (strip) hipLaunchKernelGGL(k_conv3x3_wgrad_strip_bf16d<P>, grid, dim3(256), 0, st, a);
-    else if (dma && nbuf == 2) hipLaunchKernelGGL((k_conv3x3_wgrad_win_bf16d<P, 2>), grid, dim3(256), 0, st, a);
-    else if (dma) hipLaunchKernelGGL((k_conv3x3_wgrad_win_bf16d<P, 3>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_conv3x3_wgrad_win_bf16p<P>, grid, dim3(256), 0, st, a);
-    if (prof_enabled()) prof_pop(st);
+    if (strip2) launch_gemm(k_conv3x3_wgrad_strip2_bf16d<P == 32 ? 32 : 16>, KName{"k_conv3x3_wgrad_strip2_bf16d", 1, {P}}, grid, a, st);
+    else if (strip) launch_gemm(k_conv3x3_wgrad_strip_bf16d<P>, KName{"k_conv3x3_wgrad_strip_bf16d", 1, {P}}, grid, a, st);
+    else if (dma && wg_nbuf() == 2) launch_gemm(k_conv3x3_wgrad_win_bf16d<P, 2>, KName{"k_conv3x3_wgrad_win_bf16d", 2, {P, 2}}, grid, a, st);
+    else if (dma) launch_gemm(k_conv3x3_wgrad_win_bf16d<P, 3>, KName{"k_conv3x3_wgrad_win_bf16d", 2, {P, 3}}, grid, a, st);
+    else launch_gemm(k_conv3x3_wgrad_win_bf16p<P>, KName{"k_conv3x3_wgrad_win_bf16p", 1, {P}}, grid, a, st);
     if (s > 1) finish_slabs(slab, s, per, dw, st);
 }
 
@@ -1357,11 +1268,7 @@ void conv3x3_wgrad_ps(Split dz, int cout, Split x, int cin, float* dw, int B, in
         W % 2 == 0 && slab && slab_cap >= 2 * kPairPer && wg_pair32()) {
         const int P = wgrad_win_ps_stage(64, 64, W / 2);
         if (P) {
-            GemmArgs a{};
-            a.M = 64; a.N = 576; a.K = B * H * (W / 2);
-            a.B = B; a.H = H; a.W = W / 2;
-            a.A = (const float*)dz.p; a.lda = 64; a.a_coff = 0;
-            a.Bm = (const float*)x.p; a.ldb = 64; a.b_coff = 0; a.b_cin = 64;
+            GemmArgs a = wgrad_args(Split{dz.p, 64, 0}, 64, Split{x.p, 64, 0}, 576, 64, B, H, W / 2);
             float* pr = slab + (slab_cap - kPairPer);   // the pair product, after the split-K slabs
             switch (P) {
                 case 64: launch_wgrad_win_ps1<64>(a, pr, slab, slab_cap - kPairPer, st); break;
@@ -1372,32 +1279,18 @@ void conv3x3_wgrad_ps(Split dz, int cout, Split x, int cin, float* dw, int B, in
             return;
         }
     }
-    GemmArgs a{};
-    a.M = cout; a.N = 9 * cin; a.K = B * H * W;
-    a.B = B; a.H = H; a.W = W;
-    a.A = (const float*)dz.p; a.lda = dz.ld; a.a_coff = dz.coff;
-    a.Bm = (const float*)x.p; a.ldb = x.ld; a.b_coff = x.coff; a.b_cin = cin;
+    GemmArgs a = wgrad_args(dz, cout, x, 9 * cin, cin, B, H, W);
     if (!g_no_wgwin)
         switch (wgrad_win_ps_stage(cout, cin, W)) {
             case 64: launch_wgrad_win_ps1<64>(a, dw, slab, slab_cap, st); return;
             case 32: launch_wgrad_win_ps1<32>(a, dw, slab, slab_cap, st); return;
             case 16: launch_wgrad_win_ps1<16>(a, dw, slab, slab_cap, st); return;
         }
-    const Cfg c = pick_cfg(a.M, a.N);
-    const int kb = ps_kb(false, c);
-    int s = plan_splits(a, c, kb, slab_cap, 2 * kMaxPlanes * std::max<int64_t>(dz.ld, x.ld));
-    a.kstages_per_split = cdiv(cdiv(a.K, kb), s);
-    s = cdiv(cdiv(a.K, kb), a.kstages_per_split);
-    const int64_t per = (int64_t)a.M * a.N;
-    a.ldc = a.N; a.slab_stride = per;
-    a.C = s == 1 ? dw : slab;
-    launch_kb<KConvWgradP1, 32>(c, kb, a, s, st);
-    if (s > 1) finish_slabs(slab, s, per, dw, st);
+    launch_wgrad_ps<KConvWgradP1<>>(a, dw, slab, slab_cap, 2 * kMaxPlanes * std::max<int64_t>(dz.ld, x.ld), st);
 }
 
 int dense_stats_rows(int64_t M, int N) { return cdiv(M, tile_m(pick_cfg((int)M, N))); }
 
-void launch_dense_dma(void (*fn)(GemmArgs), const char* name, const GemmArgs& a, hipStream_t st);
 void dense_fwd_ps(Split x, int K, Split w, int N, float* y, int64_t ldy, int ycoff, int64_t M, float* stats,
                   hipStream_t st, bool y_bf16, const float* add, const float* mask, int64_t ldadd) {
     if (mask && !add) throw std::runtime_error("dense GEMM: a mask needs the added matrix");
@@ -1412,12 +1305,8 @@ void dense_fwd_ps(Split x, int K, Split w, int N, float* y, int64_t ldy, int yco
                   aview(add == y && ldadd == ldy ? nullptr : add, M, ldadd, ldadd == ldy ? ycoff : 0, N, 4, "add"),
                   aview(mask, M, ldy, ycoff, N, 4, "mask")});
     if (M > INT32_MAX) throw std::runtime_error("dense GEMM: too many rows");
-    GemmArgs a{};
-    a.M = (int)M; a.N = N; a.K = K;
-    a.B = 1; a.H = 1; a.W = (int)M;
-    a.A = (const float*)x.p; a.lda = x.ld; a.a_coff = x.coff;
-    a.Bm = (const float*)w.p; a.ldb = w.ld; a.b_coff = w.coff;
-    a.C = y; a.ldc = ldy; a.c_coff = ycoff;
+    GemmArgs a = gemm_args((int)M, N, K, 1, 1, (int)M, x, w);
+    out_args(a, y, ldy, ycoff);
     a.stats = stats;
     a.bias = add;
     a.C2 = const_cast<float*>(mask);
@@ -1425,6 +1314,7 @@ void dense_fwd_ps(Split x, int K, Split w, int N, float* y, int64_t ldy, int yco
     const Cfg c = pick_cfg(a.M, a.N);
     const int kb = ps_kb(true, c);
     a.kstages_per_split = cdiv(a.K, kb);
+    const bool add_ld = add && ldadd != ldy;
     // the LDS-DMA dense GEMM on 128 x 128 tiles (config 5's 1x1 / im2col forward GEMMs: 571.5 -> 575.2
     // img/s on one box); CAD_DENSEDMA=0 keeps the register-staged gemm_body_ps kernels
     static const bool ddma = [] {
@@ -1432,35 +1322,19 @@ void dense_fwd_ps(Split x, int K, Split w, int N, float* y, int64_t ldy, int yco
         return !(e && e[0] == '0');
     }();
     if (ddma && c == C22 && K % 8 == 0 && x.ld % 8 == 0 && x.coff % 8 == 0 && w.ld % 8 == 0 && w.coff % 8 == 0) {
-        if (add && (stats || y_bf16)) throw std::runtime_error("dense GEMM: the added matrix needs fp32 output");
-        if (add && mask)
-            launch_dense_dma(k_dense_bf16d<EpiStoreAddMask>, "void cad::k_dense_bf16d<cad::EpiStoreAddMask>(cad::GemmArgs)", a, st);
-        else if (add && ldadd != ldy)
-            launch_dense_dma(k_dense_bf16d<EpiStoreAddLd>, "void cad::k_dense_bf16d<cad::EpiStoreAddLd>(cad::GemmArgs)", a, st);
-        else if (add) launch_dense_dma(k_dense_bf16d<EpiStoreAdd>, "void cad::k_dense_bf16d<cad::EpiStoreAdd>(cad::GemmArgs)", a, st);
-        else if (y_bf16 && stats)
-            launch_dense_dma(k_dense_bf16d<EpiStoreStatsB16>, "void cad::k_dense_bf16d<cad::EpiStoreStatsB16>(cad::GemmArgs)", a, st);
-        else if (y_bf16) launch_dense_dma(k_dense_bf16d<EpiStoreB16>, "void cad::k_dense_bf16d<cad::EpiStoreB16>(cad::GemmArgs)", a, st);
-        else if (stats) launch_dense_dma(k_dense_bf16d<EpiStoreStats>, "void cad::k_dense_bf16d<cad::EpiStoreStats>(cad::GemmArgs)", a, st);
-        else launch_dense_dma(k_dense_bf16d<EpiStore>, "void cad::k_dense_bf16d<cad::EpiStore>(cad::GemmArgs)", a, st);
+        with_dense_epi<true>(add, add_ld, mask, stats, y_bf16, [&](auto e) {
+            using Epi = decltype(e);
+            launch_gemm(k_dense_bf16d<Epi>, KName{"k_dense_bf16d", 0, {}, Epi::name}, dim3(cdiv(a.M, 128), cdiv(a.N, 128), 1), a, st);
+        });
         return;
     }
-    if (add && ldadd != ldy) {   // (the register-staged kernels: the GEMM, then an add pass)
-        if (stats || y_bf16) throw std::runtime_error("dense GEMM: the added matrix needs fp32 output");
-        a.bias = nullptr;
-        launch_kb<KDenseP1, 32, 64>(c, kb, a, 1, st);
-        add_strided(y, ldy, add, ldadd, 0, N, 1, 1, (int)M, 1, st);
-    } else if (add) {
-        if (stats || y_bf16) throw std::runtime_error("dense GEMM: the added matrix needs fp32 output");
-        launch_kb<KDenseAddP1, 32, 64>(c, kb, a, 1, st);
-        if (mask) mask_inplace(y, ldy, ycoff, mask, N, M, st);   // (the register-staged kernels: a pass)
-    } else if (y_bf16) {
-        if (stats) launch_kb<KDenseSP1B, 32, 64>(c, kb, a, 1, st);
-        else launch_kb<KDenseP1B, 32, 64>(c, kb, a, 1, st);
-    } else {
-        if (stats) launch_kb<KDenseSP1, 32, 64>(c, kb, a, 1, st);
-        else launch_kb<KDenseP1, 32, 64>(c, kb, a, 1, st);
-    }
+    // the register-staged kernels add a matrix of its own stride, and mask, in a pass after the GEMM
+    if (add && (stats || y_bf16)) throw std::runtime_error("dense GEMM: the added matrix needs fp32 output");
+    if (add_ld) a.bias = nullptr;
+    with_dense_epi<false>(add && !add_ld, false, false, stats, y_bf16,
+                          [&](auto e) { launch_kb<KDenseP1<decltype(e)>, 32, 64>(c, kb, a, 1, st); });
+    if (add_ld) add_strided(y, ldy, add, ldadd, 0, N, 1, 1, (int)M, 1, st);
+    else if (add && mask) mask_inplace(y, ldy, ycoff, mask, N, M, st);
 }
 
 void dense_wgrad_ps(Split dz, int N, Split x, int K, float* dw, int64_t ldw, int64_t M, float* slab, int64_t slab_cap,
@@ -1471,21 +1345,8 @@ void dense_wgrad_ps(Split dz, int N, Split x, int K, float* dw, int64_t ldw, int
                  {aview(dz.p, M, dz.ld, dz.coff, N, 2, "dz"), aview(x.p, M, x.ld, x.coff, K, 2, "x")});
     if (ldw != K) throw std::runtime_error("dense wgrad: dw rows must be dense");
     if (M > INT32_MAX) throw std::runtime_error("dense GEMM: too many rows");
-    GemmArgs a{};
-    a.M = N; a.N = K; a.K = (int)M;
-    a.B = 1; a.H = 1; a.W = (int)M;
-    a.A = (const float*)dz.p; a.lda = dz.ld; a.a_coff = dz.coff;
-    a.Bm = (const float*)x.p; a.ldb = x.ld; a.b_coff = x.coff;
-    const Cfg c = pick_cfg(a.M, a.N);
-    const int kb = ps_kb(false, c);
-    int s = plan_splits(a, c, kb, slab_cap, 2 * kMaxPlanes * std::max<int64_t>(dz.ld, x.ld));
-    a.kstages_per_split = cdiv(cdiv(a.K, kb), s);
-    s = cdiv(cdiv(a.K, kb), a.kstages_per_split);
-    const int64_t per = (int64_t)a.M * a.N;
-    a.ldc = a.N; a.slab_stride = per;
-    a.C = s == 1 ? dw : slab;
-    launch_kb<KDenseWgradP1, 32>(c, kb, a, s, st);
-    if (s > 1) finish_slabs(slab, s, per, dw, st);
+    GemmArgs a = wgrad_args(dz, N, x, K, 0, 1, 1, (int)M);
+    launch_wgrad_ps<KDenseWgradP1<>>(a, dw, slab, slab_cap, 2 * kMaxPlanes * std::max<int64_t>(dz.ld, x.ld), st);
 }
 
 // CAD_BIGT bit 1: ConvT forward, bit 2: ConvT dgrad on the 256 x 128 tiles (bf16 outputs).  Measured at
@@ -1497,16 +1358,6 @@ int bigt_mask() {
     }();
     return m;
 }
-void launch_big(void (*fn)(GemmArgs), const char* name, const GemmArgs& a, hipStream_t st) {
-    const dim3 grid(cdiv(a.M, 256), cdiv(a.N, 128), 1);
-    if (prof_enabled()) {
-        prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
-        prof_pop(st);
-    } else {
-        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
-    }
-}
 // CAD_CONVTDMA bit 1: the bf16 ConvT forward on the LDS-DMA dense GEMM.  Measured at configs[3] (4
 // launches per step): 1.47 -> 1.42 ms (default on).  (Its up-gather input-gradient form, 1.13 ms
 // against the 256 x 128 tiles' 1.11, was removed in round 5.)
@@ -1517,41 +1368,22 @@ int convt_dma() {
     }();
     return m;
 }
-void launch_dense_dma(void (*fn)(GemmArgs), const char* name, const GemmArgs& a, hipStream_t st) {
-    const dim3 grid(cdiv(a.M, 128), cdiv(a.N, 128), 1);
-    if (prof_enabled()) {
-        prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
-        prof_pop(st);
-    } else {
-        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, a);
-    }
-}
 void convT_fwd_ps(Split x, int cin, Split wf, const float* bias, int cout, float* y, int64_t ldy, int ycoff, int B,
                   int H, int W, hipStream_t st, bool y_bf16) {
     ps_check(x, cin, "convT_fwd x");
     ps_check(wf, cin, "convT_fwd w");
     CAD_NO_ALIAS("convT_fwd_ps", {aview(y, (int64_t)B * 4 * H * W, ldy, ycoff, cout, y_bf16 ? 2 : 4, "y")},
                  {aview(x.p, (int64_t)B * H * W, x.ld, x.coff, cin, 2, "x"), aview(wf.p, 4 * cout, wf.ld, wf.coff, cin, 2, "w")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = 4 * cout; a.K = cin;
-    a.B = B; a.H = H; a.W = W;
-    a.A = (const float*)x.p; a.lda = x.ld; a.a_coff = x.coff;
-    a.Bm = (const float*)wf.p; a.ldb = wf.ld; a.b_coff = wf.coff;
-    a.C = y; a.ldc = ldy; a.c_coff = ycoff; a.bias = bias;
+    GemmArgs a = convT_fwd_args(x, cin, wf, bias, cout, y, ldy, ycoff, B, H, W);
     const Cfg c = pick_cfg(a.M, a.N);
     const int kb = ps_kb(false, c);
     a.kstages_per_split = cdiv(a.K, kb);
-    if (y_bf16 && (convt_dma() & 1) && a.N >= 128 && a.K % 8 == 0 && a.lda % 8 == 0 && a.a_coff % 8 == 0) {
-        launch_dense_dma(k_convT_fwd_bf16dt, "void cad::k_convT_fwd_bf16dt(cad::GemmArgs)", a, st);
-        return;
-    }
-    if (y_bf16 && (bigt_mask() & 1) && a.N >= 128 && a.M >= 4096) {
-        launch_big(k_convT_fwd_bf16pt4<32>, "void cad::k_convT_fwd_bf16pt4<32>(cad::GemmArgs)", a, st);
-        return;
-    }
-    if (y_bf16) launch_kb<KConvTFwdP1T, 32>(c, kb, a, 1, st);
-    else launch_kb<KConvTFwdP1, 32>(c, kb, a, 1, st);
+    if (y_bf16 && (convt_dma() & 1) && a.N >= 128 && a.K % 8 == 0 && a.lda % 8 == 0 && a.a_coff % 8 == 0)
+        launch_gemm(k_convT_fwd_bf16dt, KName{"k_convT_fwd_bf16dt"}, dim3(cdiv(a.M, 128), cdiv(a.N, 128), 1), a, st);
+    else if (y_bf16 && (bigt_mask() & 1) && a.N >= 128 && a.M >= 4096)
+        launch_gemm(k_convT_fwd_bf16pt4<32>, KName{"k_convT_fwd_bf16pt4", 1, {32}}, dim3(cdiv(a.M, 256), cdiv(a.N, 128), 1), a, st);
+    else if (y_bf16) launch_kb<KConvTFwdP1T<>, 32>(c, kb, a, 1, st);
+    else launch_kb<KConvTFwdP1<>, 32>(c, kb, a, 1, st);
 }
 
 void convT_dgrad_ps(Split g, int cout, Split wm, int cin, float* dx, int B, int H, int W, hipStream_t st, bool dx_bf16) {
@@ -1559,21 +1391,14 @@ void convT_dgrad_ps(Split g, int cout, Split wm, int cin, float* dx, int B, int 
     ps_check(wm, 4 * cout, "convT_dgrad w");
     CAD_NO_ALIAS("convT_dgrad_ps", {aview(dx, (int64_t)B * H * W, cin, 0, cin, dx_bf16 ? 2 : 4, "dx")},
                  {aview(g.p, (int64_t)B * 4 * H * W, g.ld, g.coff, cout, 2, "g"), aview(wm.p, cin, wm.ld, wm.coff, 4 * cout, 2, "w")});
-    GemmArgs a{};
-    a.M = B * H * W; a.N = cin; a.K = 4 * cout;
-    a.B = B; a.H = H; a.W = W;
-    a.A = (const float*)g.p; a.lda = g.ld; a.a_coff = g.coff; a.a_cin = cout;
-    a.Bm = (const float*)wm.p; a.ldb = wm.ld; a.b_coff = wm.coff;
-    a.C = dx; a.ldc = cin; a.c_coff = 0;
+    GemmArgs a = convT_dgrad_args(g, cout, wm, cin, dx, B, H, W);
     const Cfg c = pick_cfg(a.M, a.N);
     const int kb = ps_kb(false, c);
     a.kstages_per_split = cdiv(a.K, kb);
-    if (dx_bf16 && (bigt_mask() & 2) && a.N >= 128 && a.M >= 4096) {
-        launch_big(k_convT_dgrad_bf16pb4<32>, "void cad::k_convT_dgrad_bf16pb4<32>(cad::GemmArgs)", a, st);
-        return;
-    }
-    if (dx_bf16) launch_kb<KConvTDgradP1B, 32>(c, kb, a, 1, st);
-    else launch_kb<KConvTDgradP1, 32>(c, kb, a, 1, st);
+    if (dx_bf16 && (bigt_mask() & 2) && a.N >= 128 && a.M >= 4096)
+        launch_gemm(k_convT_dgrad_bf16pb4<32>, KName{"k_convT_dgrad_bf16pb4", 1, {32}}, dim3(cdiv(a.M, 256), cdiv(a.N, 128), 1), a, st);
+    else if (dx_bf16) launch_kb<KConvTDgradP1B<>, 32>(c, kb, a, 1, st);
+    else launch_kb<KConvTDgradP1<>, 32>(c, kb, a, 1, st);
 }
 
 void convT_wgrad_ps(Split x, int cin, Split g, int cout, float* dw, int B, int H, int W, float* slab,
@@ -1584,21 +1409,8 @@ void convT_wgrad_ps(Split x, int cin, Split g, int cout, float* dw, int B, int H
                  {aview(dw, cin, 4 * cout, 0, 4 * cout, 4, "dw"), aview(slab, 1, slab_cap, 0, slab ? slab_cap : 0, 4, "slab")},
                  {aview(x.p, (int64_t)B * H * W, x.ld, x.coff, cin, 2, "x"),
                   aview(g.p, (int64_t)B * 4 * H * W, g.ld, g.coff, cout, 2, "g")});
-    GemmArgs a{};
-    a.M = cin; a.N = 4 * cout; a.K = B * H * W;
-    a.B = B; a.H = H; a.W = W;
-    a.A = (const float*)x.p; a.lda = x.ld; a.a_coff = x.coff;
-    a.Bm = (const float*)g.p; a.ldb = g.ld; a.b_coff = g.coff; a.b_cin = cout;
-    const Cfg c = pick_cfg(a.M, a.N);
-    const int kb = ps_kb(false, c);
-    int s = plan_splits(a, c, kb, slab_cap, 2 * kMaxPlanes * std::max<int64_t>(x.ld, 4 * g.ld));
-    a.kstages_per_split = cdiv(cdiv(a.K, kb), s);
-    s = cdiv(cdiv(a.K, kb), a.kstages_per_split);
-    const int64_t per = (int64_t)a.M * a.N;
-    a.ldc = a.N; a.slab_stride = per;
-    a.C = s == 1 ? dw : slab;
-    launch_kb<KConvTWgradP1, 32>(c, kb, a, s, st);
-    if (s > 1) finish_slabs(slab, s, per, dw, st);
+    GemmArgs a = wgrad_args(x, cin, g, 4 * cout, cout, B, H, W);
+    launch_wgrad_ps<KConvTWgradP1<>>(a, dw, slab, slab_cap, 2 * kMaxPlanes * std::max<int64_t>(x.ld, 4 * g.ld), st);
 }
 
 }  // namespace cad

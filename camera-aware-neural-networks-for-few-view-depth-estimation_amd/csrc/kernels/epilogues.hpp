@@ -5,9 +5,13 @@
 
 namespace cad {
 
+// Every functor carries `name`, its type as rocprofv3 prints it: the host launchers build a kernel's
+// profiler name from it (kernels.hpp KName).  Host-side only; no device code reads it.
+//
 // Row-major epilogues: C[m][c_coff + n] with row stride ldc; the engine stores through a buffer
 // descriptor based at row_base (gemm_mfma.hpp gemm_epilogue).
 struct EpiStore {
+    static constexpr const char* name = "cad::EpiStore";
     static constexpr bool STATS = false;
     static constexpr bool BF16 = false;
     static constexpr bool ADD = false;
@@ -17,12 +21,14 @@ struct EpiStore {
     }
 };
 struct EpiStoreStats : EpiStore {
+    static constexpr const char* name = "cad::EpiStoreStats";
     static constexpr bool STATS = true;
 };
 // C[m][n] = acc + R[m][n], R = a.bias read as a matrix with C's row stride and channel offset (the
 // config-5 bottleneck's identity shortcut gradient added in the dgrad that produces the block-input
 // gradient: no separate add pass)
 struct EpiStoreAdd : EpiStore {
+    static constexpr const char* name = "cad::EpiStoreAdd";
     static constexpr bool ADD = true;
     __device__ static const float* add_base(const GemmArgs& a, int m0) {
         return a.bias + (int64_t)m0 * a.ldc + a.c_coff;
@@ -31,12 +37,14 @@ struct EpiStoreAdd : EpiStore {
 // ... with the added matrix's own row stride a.ldc2 (config 5: a decoder concat's skip-half gradient
 // added to the block-output gradient a projection block's conv1 dgrad produces)
 struct EpiStoreAddLd : EpiStoreAdd {
+    static constexpr const char* name = "cad::EpiStoreAddLd";
     static constexpr bool ADD_LD = true;
     __device__ static const float* add_base(const GemmArgs& a, int m0) { return a.bias + (int64_t)m0 * a.ldc2; }
 };
 // ... then zeroed where the fp32 matrix a.C2 (same rows / offset as C) is not > 0: config 5's block-input
 // gradient masked by the previous block's ReLU output (the separate k_relu_mask pass, fused)
 struct EpiStoreAddMask : EpiStoreAdd {
+    static constexpr const char* name = "cad::EpiStoreAddMask";
     static constexpr bool MASK = true;
     __device__ static const float* mask_base(const GemmArgs& a, int m0) {
         return static_cast<const float*>(a.C2) + (int64_t)m0 * a.ldc + a.c_coff;
@@ -45,6 +53,7 @@ struct EpiStoreAddMask : EpiStoreAdd {
 // bf16 outputs (round-to-nearest-even; a.C addresses bf16 rows of ldc elements): the pre-BN conv
 // outputs of the bf16 engine.  BN partials are taken from the rounded values BN normalises.
 struct EpiStoreB16 {
+    static constexpr const char* name = "cad::EpiStoreB16";
     static constexpr bool STATS = false;
     static constexpr bool BF16 = true;
     static constexpr bool ADD = false;
@@ -54,11 +63,13 @@ struct EpiStoreB16 {
     }
 };
 struct EpiStoreStatsB16 : EpiStoreB16 {
+    static constexpr const char* name = "cad::EpiStoreStatsB16";
     static constexpr bool STATS = true;
 };
 // window epilogue only: columns [0, split_n) fp32 into C, [split_n, N) bf16 into C2 (the decoder conv1
 // dgrad writes dcat's skip half for the encoder's BN backward and the up half straight into the twin
-// the ConvT gradients read)
+// the ConvT gradients read).  Both split stores keep their base's `name`: the launch profiles have always
+// listed them as cad::EpiStore / cad::EpiStoreB16.
 struct EpiStoreSplitB16 : EpiStore {
     static constexpr bool SPLIT = true;
 };
@@ -74,6 +85,7 @@ struct EpiStoreSplit2B16 : EpiStoreB16 {
 // column-reduction pass over (dL/da1, y) is then not needed.
 template <bool OB16, bool YB>
 struct EpiStoreBnSums {
+    static constexpr const char* name = "cad::EpiStoreBnSums";   // (bare: the launch profiles carry no arguments)
     static constexpr bool STATS = false;
     static constexpr bool BF16 = OB16;
     static constexpr bool ADD = false;
@@ -92,6 +104,8 @@ struct EpiStoreBnSums {
 // Served by all three epilogue bodies (gemm_epilogue_t, win_epilogue, win_epilogue16); no BN partials.
 template <bool OB16, bool FILM_>
 struct EpiStoreAct {
+    static constexpr const char* name = OB16 ? (FILM_ ? "cad::EpiStoreAct<true, true>" : "cad::EpiStoreAct<true, false>")
+                                             : (FILM_ ? "cad::EpiStoreAct<false, true>" : "cad::EpiStoreAct<false, false>");
     static constexpr bool STATS = false;
     static constexpr bool BF16 = OB16;
     static constexpr bool ADD = false;
@@ -114,6 +128,7 @@ struct EpiStoreAct {
 // concat, written straight into the consumers' twin); fp32 otherwise.
 template <bool OB16>
 struct EpiConvTOut {
+    static constexpr const char* name = OB16 ? "cad::EpiConvTOut<true>" : "cad::EpiConvTOut<false>";
     static constexpr bool STATS = false;
     static constexpr bool BF16 = false;   // (row-major store path unused: structured)
     static constexpr bool ADD = false;
@@ -227,6 +242,7 @@ struct EpiConvTOut {
 using EpiConvT = EpiConvTOut<false>;
 using EpiConvTB16 = EpiConvTOut<true>;
 struct EpiSlab {   // split-K partial: slab z holds C[m][n] of K-slice z
+    static constexpr const char* name = "cad::EpiSlab";
     static constexpr bool STATS = false;
     static constexpr bool BF16 = false;
     static constexpr bool ADD = false;

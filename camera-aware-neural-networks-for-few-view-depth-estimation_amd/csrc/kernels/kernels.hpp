@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdio>
 #include <initializer_list>
 
 namespace cad {
@@ -14,6 +15,50 @@ namespace cad {
 bool prof_enabled();
 void prof_push(const char* name, double flops, hipStream_t st);
 void prof_pop(hipStream_t st);
+
+// A GEMM kernel's profiler name, the symbol as rocprofv3 demangles it:
+//   void cad::<base><v[0], .. v[nv-1], epi, tail>(<params>)
+// nv integers, then the epilogue (Epi::name, epilogues.hpp), then a trailing argument; each part optional.
+// Formatted only when the profiler is on.
+struct KName {
+    const char* base;
+    int nv = 0;
+    int v[3] = {0, 0, 0};
+    const char* epi = nullptr;
+    const char* tail = nullptr;
+    const char* params = "cad::GemmArgs";
+    void format(char* buf, size_t n) const {
+        int at = snprintf(buf, n, "void cad::%s", base);
+        const char* sep = "<";
+        auto put = [&](const char* fmt, auto x) {
+            if (at < (int)n) at += snprintf(buf + at, n - at, fmt, sep, x);
+            sep = ", ";
+        };
+        for (int i = 0; i < nv; ++i) put("%s%d", v[i]);
+        if (epi) put("%s%s", epi);
+        if (tail) put("%s%s", tail);
+        if (at < (int)n) snprintf(buf + at, n - at, "%s(%s)", sep[0] == '<' ? "" : ">", params);
+    }
+};
+inline const char* prof_name(const char* literal, char*, size_t) { return literal; }
+inline const char* prof_name(const KName& k, char* buf, size_t n) { return k.format(buf, n), buf; }
+// The one launch path of the profiled kernels (256 threads, no dynamic LDS): the profiler bracket around
+// the launch.  `name`: a KName or a literal.  Allocates nothing.
+template <class Name, class... KA, class... A>
+void launch_prof(void (*fn)(KA...), const Name& name, double flops, dim3 grid, hipStream_t st, const A&... args) {
+    const bool prof = prof_enabled();
+    if (prof) {
+        char buf[160];
+        prof_push(prof_name(name, buf, sizeof buf), flops, st);
+    }
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, args...);
+    if (prof) prof_pop(st);
+}
+// ... of a GEMM on GemmArgs `a` (gemm_mfma.hpp; `extra`: kernel arguments after it): 2 M N K FLOPs
+template <class Name, class Args, class... KA, class... X>
+void launch_gemm(void (*fn)(Args, KA...), const Name& name, dim3 grid, const Args& a, hipStream_t st, const X&... extra) {
+    launch_prof(fn, name, 2.0 * a.M * a.N * (double)a.K, grid, st, a, extra...);
+}
 
 // ---------------- launch-level aliasing guard (host/alias.cpp) ----------------
 // CAD_ALIAS_CHECK=1 (tests/conftest.py sets it): an instrumented launcher refuses a launch whose output
@@ -49,14 +94,8 @@ void alias_check_impl(const char* op, std::initializer_list<AliasView> outs, std
 // 2 = B1: bf16-rounded operands, fp32 accumulation
 void set_gemm_engine(int e);
 int gemm_engine();
-// y = conv3x3(x) (+ per-tile BN partials [rows][2][cout] when stats != nullptr)
-// wtwin (here and in conv3x3_dgrad / conv3x3_dgrad_bnsums): the weights' three-plane twin (below), read
-// by the S3 window kernels instead of splitting w in their loaders; nullptr, or a shape the window
-// kernels do not serve: the in-loader split.  Same bits either way.
-void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y,
-                 int64_t ldy, int ycoff, int B, int H, int W, float* stats, hipStream_t st, const void* wtwin = nullptr);
-// The eval-mode forward's fused convolutions (EpiStoreAct, epilogues.hpp): conv3x3_fwd / conv3x3_fwd_ps with the
-// block's BatchNorm + ReLU and, when gam / bet are given, its FiLM modulation applied in the GEMM epilogue:
+// The eval-mode forward's fused epilogue (EpiStoreAct, epilogues.hpp): the block's BatchNorm + ReLU and, when
+// gam / bet are given, its FiLM modulation applied to the finished accumulator:
 //   y[p][n] = max(fma(conv, scale[n], shift[n]), 0)                      gam == nullptr
 //   y[p][n] = gam[b][n] * max(conv * scale[n] + shift[n], 0) + bet[b][n]  b = p / (H W)
 // scale / shift: cout floats (bn_eval_coeffs); gam / bet: [B][cout] (film_mlp_fwd_all), both or neither.  The
@@ -67,9 +106,20 @@ struct ActCoeffs {
     const float* gam = nullptr;
     const float* bet = nullptr;
 };
-// fp32 operands on the current engine (window kernels where conv3x3_fwd takes them), fp32 y
-void conv3x3_fwd_act(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y, int64_t ldy,
-                     int ycoff, int B, int H, int W, const ActCoeffs& act, hipStream_t st, const void* wtwin = nullptr);
+// What a conv3x3 forward does with its output: store it (neither), store it with the per-tile BN partials
+// [rows][2][cout] (stats), or store the eval-mode activation (act).  Both at once: std::invalid_argument.
+struct ConvEpi {
+    float* stats = nullptr;
+    const ActCoeffs* act = nullptr;
+    ConvEpi(float* s = nullptr) : stats(s) {}
+    ConvEpi(const ActCoeffs& a) : act(&a) {}
+};
+// y = conv3x3(x), fp32 operands on the current engine, fp32 y
+// wtwin (here and in conv3x3_dgrad / conv3x3_dgrad_bnsums): the weights' three-plane twin (below), read
+// by the S3 window kernels instead of splitting w in their loaders; nullptr, or a shape the window
+// kernels do not serve: the in-loader split.  Same bits either way.
+void conv3x3_fwd(const float* x, int64_t ldx, int xcoff, int cin, const float* w, int cout, float* y,
+                 int64_t ldy, int ycoff, int B, int H, int W, ConvEpi epi, hipStream_t st, const void* wtwin = nullptr);
 // Weight twin of a 3 x 3 convolution for the S3 window kernels: the three bf16 planes of split3 of
 // Wt[n][tap * cin + ci] (forward: n = cout, the OHWI parameters; dgrad: the repack, n and cin swapped) in
 // the kernels' LDS-image order, one 9 * bn * 32-byte block per (N tile of bn rows, stage (cb, ky)):
@@ -112,13 +162,10 @@ constexpr int kMaxPlanes = 1;          // twin bytes = elems * 2 * kMaxPlanes
 // out[row][ocoff + c] (split, ld ldo) = split(x[row][xcoff + c]), c < C, rows < M
 void split_rows(const float* x, int64_t ldx, int xcoff, int C, int64_t M, void* out, int64_t ldo, int ocoff,
                 hipStream_t st);
-// y_bf16: y is written as bf16 rows of ldy elements (the bf16 engine's pre-BN outputs)
-void conv3x3_fwd_ps(Split x, int cin, Split w, int cout, float* y, int64_t ldy, int ycoff, int B, int H, int W,
-                    float* stats, hipStream_t st, bool y_bf16 = false);
-// ... on the pre-split twins (bf16 engine); y: fp32 rows, or with y_bf16 bf16 rows (the consumer's twin),
-// rounded once from the fp32 activation
-void conv3x3_fwd_ps_act(Split x, int cin, Split w, int cout, void* y, int64_t ldy, int ycoff, int B, int H, int W,
-                        const ActCoeffs& act, hipStream_t st, bool y_bf16);
+// y_bf16: y is written as bf16 rows of ldy elements (the bf16 engine's pre-BN outputs; an activation: the
+// consumer's twin, rounded once from the fp32 value)
+void conv3x3_fwd_ps(Split x, int cin, Split w, int cout, void* y, int64_t ldy, int ycoff, int B, int H, int W,
+                    ConvEpi epi, hipStream_t st, bool y_bf16 = false);
 // dx_bf16: dx is written as bf16 rows of lddx elements (the bf16 engine's conv2 input gradient).
 // hi != nullptr: columns [split_n, cin) go to the bf16 rows hi (ldhi elements) instead of dx when the
 // window kernel runs and split_n % 32 == 0 (returns true); otherwise all of dx is written as fp32

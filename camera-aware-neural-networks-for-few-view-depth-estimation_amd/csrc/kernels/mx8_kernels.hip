@@ -92,24 +92,12 @@ void check_view(const Mx8& m, const char* what) {
         throw std::runtime_error(std::string("MX-fp8 operand layout: ") + what);
 }
 
-template <class Epi>
-const char* epi_name() {
-    return Epi::STATS ? (Epi::BF16 ? "EpiStoreStatsB16" : "EpiStoreStats") : (Epi::BF16 ? "EpiStoreB16" : "EpiStore");
-}
+constexpr const char* kX8Params = "cad::GemmArgs, cad::Mx8, cad::Mx8";
 
 template <int WM, int WN, class Epi>
 void launch_dense(const GemmArgs& a, const Mx8& x, const Mx8& w, hipStream_t st) {
-    const dim3 grid(cdiv(a.M, 64 * WM), cdiv(a.N, 64 * WN));
-    if (prof_enabled()) {
-        char name[160];
-        std::snprintf(name, sizeof name, "void cad::k_dense_x8<%d, %d, cad::%s>(cad::GemmArgs, cad::Mx8, cad::Mx8)", WM, WN,
-                      epi_name<Epi>());
-        prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-        hipLaunchKernelGGL((k_dense_x8<WM, WN, Epi>), grid, dim3(256), 0, st, a, x, w);
-        prof_pop(st);
-    } else {
-        hipLaunchKernelGGL((k_dense_x8<WM, WN, Epi>), grid, dim3(256), 0, st, a, x, w);
-    }
+    launch_gemm(k_dense_x8<WM, WN, Epi>, KName{"k_dense_x8", 2, {WM, WN}, Epi::name, nullptr, kX8Params},
+                dim3(cdiv(a.M, 64 * WM), cdiv(a.N, 64 * WN)), a, st, x, w);
 }
 template <class Epi>
 void launch_dense_cfg(const GemmArgs& a, const Mx8& x, const Mx8& w, hipStream_t st) {
@@ -139,17 +127,8 @@ WinX8 pick_win_x8(int cin, int W, int N) {
 template <int R, int CW, class Epi>
 void launch_win_x8_1(const GemmArgs& a, const Mx8& x, const Mx8& w, hipStream_t st) {
     constexpr int BN = R * CW == 128 ? 128 : 64;
-    const dim3 grid(a.B * cdiv(a.H, R) * (a.W / CW), cdiv(a.N, BN));
-    if (prof_enabled()) {
-        char name[160];
-        std::snprintf(name, sizeof name, "void cad::k_conv3x3_win_x8<%d, %d, cad::%s>(cad::GemmArgs, cad::Mx8, cad::Mx8)", R,
-                      CW, epi_name<Epi>());
-        prof_push(name, 2.0 * a.M * a.N * (double)a.K, st);
-        hipLaunchKernelGGL((k_conv3x3_win_x8<R, CW, Epi>), grid, dim3(256), 0, st, a, x, w);
-        prof_pop(st);
-    } else {
-        hipLaunchKernelGGL((k_conv3x3_win_x8<R, CW, Epi>), grid, dim3(256), 0, st, a, x, w);
-    }
+    launch_gemm(k_conv3x3_win_x8<R, CW, Epi>, KName{"k_conv3x3_win_x8", 2, {R, CW}, Epi::name, nullptr, kX8Params},
+                dim3(a.B * cdiv(a.H, R) * (a.W / CW), cdiv(a.N, BN)), a, st, x, w);
 }
 template <class Epi>
 void launch_win_x8(const WinX8& p, const GemmArgs& a, const Mx8& x, const Mx8& w, hipStream_t st) {
